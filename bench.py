@@ -7,7 +7,14 @@ replicas per GPU, network delay U[1 ms, 5 ms], drop 2^-10 per send
 replica on the device-resident tables and run all of them to quiescence
 (runTimedT, src/Control/TimeWarp/Timed/TimedT.hs:293-304).  An event = one
 PQ.minView pop of the TimedT schedule (TimedT.hs:242); the GPU count equals the
-oracle's (parity-checked on a sample each run).
+oracle's.
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the result line; `--dump-outputs DIR` also writes what the
+last timed step computed.  Everything else -- the CPU baseline and the parity
+sample against the oracle, the host re-draw of the device-drawn link table,
+the measured-traffic figures from profiles/, the weak line at N > 1 -- runs
+only with `--full`.
 
 Multi-GPU: one process per GPU (torchrun).  The replica configs shard
 independent replicas over the ranks with no data-path collective (only the
@@ -40,6 +47,11 @@ TABLE_CHECK_REPLICAS = 64     # replicas of a device-drawn link table re-drawn o
 HBM_PEAK_GBS = 8000.0           # MI355X HBM3E peak (MI355X_MICROARCH.md)
 BYTES_PER_EVENT = 64            # 16 B event read + 16 B event write + 32 B thread/node state r/w
 BYTES_PER_SEND = 8              # link-table entry + ordinal
+DUMP_MAX_REPLICAS = 65536       # --dump-outputs: replicas of a larger batch kept (a seeded sample)
+DUMP_MAX_HASHES = 1 << 21       # --dump-outputs: per-node trace hashes kept (16 B each: two float64 words)
+DUMP_SEED = 20240229
+DUMP_FIELDS = ("final_t", "events", "delivered", "dropped", "undeliverable", "status", "main_exc", "threads",
+               "tie_flags")
 
 
 def replica_block(args, rank: int, world: int):
@@ -82,6 +94,45 @@ def build_scenario(args, rank: int, world: int, drawer=None, max_replicas=None):
             f"gossip (config 4) one scenario of {args.nodes} nodes, fanout 4, delay U[1,5] ms, "
             f"node-partitioned over the GPUs, lookahead 1 ms windows")
     raise SystemExit(f"unknown config {args.config}")
+
+
+def _words(h):
+    """uint64 -> float64 [..., 2]: the high and low 32-bit words (both exact)."""
+    h = np.asarray(h, np.uint64)
+    return np.stack([(h >> np.uint64(32)).astype(np.float64), (h & np.uint64(0xFFFFFFFF)).astype(np.float64)],
+                    axis=-1)
+
+
+def dump_outputs(out_dir, rank, world, res, hashes, stats):
+    """--dump-outputs: what the last timed step left for its caller, as
+    float64 .npy files (the integers are below 2^53 or split into words).
+    `res`: the replicas' results (RESULT_DTYPE records); `hashes`: the
+    [replicas, nodes] trace hashes; `stats`: name -> number of the step's
+    statistics.  A batch of more than DUMP_MAX_REPLICAS replicas, and hashes
+    beyond DUMP_MAX_HASHES, are cut to a fixed seeded sample (the same rows for
+    the same arguments); hash_fold still covers every hash of every replica."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+    res = np.atleast_1d(res)
+    hashes = np.asarray(hashes, np.uint64).reshape(res.shape[0], -1)
+    R, N = hashes.shape
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = np.arange(R) if R <= DUMP_MAX_REPLICAS else np.sort(rng.choice(R, DUMP_MAX_REPLICAS, replace=False))
+    save("results", np.stack([res[f][rows].astype(np.float64) for f in DUMP_FIELDS], axis=1))
+    save("results_replicas", rows)
+    # sum over a replica's nodes of its trace hashes, mod 2^64: every hash counts
+    save("hash_fold", _words(hashes.sum(axis=1, dtype=np.uint64)[rows]))
+    n_h = max(1, min(R, DUMP_MAX_HASHES // min(N, DUMP_MAX_HASHES)))
+    hrows = np.arange(R) if n_h == R else np.sort(rng.choice(R, n_h, replace=False))
+    cols = np.arange(N) if N <= DUMP_MAX_HASHES else np.sort(rng.choice(N, DUMP_MAX_HASHES, replace=False))
+    save("hashes", _words(hashes[hrows][:, cols]))
+    save("hashes_replicas", hrows)
+    save("hashes_nodes", cols)
+    save("stats", np.array([float(v) for _, v in sorted(stats.items())]))
 
 
 def host_cpu():
@@ -230,6 +281,8 @@ def bench_gossip(args, scn, workload, world, rank, local, dist_on, barrier):
         kms += k
         windows, ticks = w, tk
     agg, h = eng.lp_results()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, agg, h, {"windows": windows, "ticks": ticks})
     if int(agg["status"]) >= 2:  # TW_REP_ABORTED or an error status on some node
         raise SystemExit(f"gossip: nodes ended in status {int(agg['status'])}")
     if dist_on and args.host_windows:
@@ -260,10 +313,11 @@ def bench_gossip(args, scn, workload, world, rank, local, dist_on, barrier):
                                            "advance kernels + collectives), up to its final stream sync"
                          if not args.host_windows else "summed event-kernel launches"},
         }
-        mt = measured_traffic(args, 1, ev, whole_loop=True) if world == 1 and not args.host_windows else None
+        mt = (measured_traffic(args, 1, ev, whole_loop=True)
+              if args.full and world == 1 and not args.host_windows else None)
         if mt:
             out["roofline"].update(mt)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import oracle
 
@@ -332,15 +386,24 @@ def main():
     ap.add_argument("--weak", action="store_true",
                     help="--replicas per GPU (weak scaling) instead of one batch split over the GPUs")
     ap.add_argument("--no-weak-line", action="store_true",
-                    help="token_ring at N > 1: skip the weak-scaling figure (a 64k batch per GPU) that is "
+                    help="--full, token_ring at N > 1: skip the weak-scaling figure (a 64k batch per GPU) that is "
                          "measured after the strong split and reported beside it as weak_line")
     ap.add_argument("--nodes", type=int, default=None, help="4096 (token_ring), 256 senders (hotspot), 1M (gossip)")
     ap.add_argument("--duration-s", type=int, default=120)
     ap.add_argument("--drop-log2", type=int, default=10)
     ap.add_argument("--round-trips", type=int, default=1000)
     ap.add_argument("--msg-num", type=int, default=1000)
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline and the parity sample "
+                         "against the oracle, the host re-draw of the device-drawn link table, the measured HBM "
+                         "traffic from profiles/, and at N > 1 the token ring's weak line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (replica results, trace hashes, "
+                         "statistics) as float64 DIR/<name>.npy (<name>_rank<r>.npy at N > 1); larger outputs as a "
+                         "fixed seeded sample")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: host seconds of the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline and the parity sample")
     ap.add_argument("--host-tables", action="store_true",
                     help="draw the link tables with the host StdGen loop instead of on the GPU")
     ap.add_argument("--geometry", default=None, choices=["dense", "sparse", "half", "wave", "narrow", "compact", "lpb"],
@@ -358,6 +421,8 @@ def main():
     ap.add_argument("--workload-key", action="store_true",
                     help="print the workload key and engine digest (tools/pmc.sh provenance) and exit")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps needs at least one timed step, --warmup none or more")
     args.weak = args.weak and not args.strong
     if args.nodes is None:
         args.nodes = {"token_ring": 4096, "hotspot": 256, "gossip": 1 << 20}.get(args.config, 2)
@@ -393,11 +458,12 @@ def main():
     # BASELINE config 3 is one 64k batch split over the GPUs (the line above);
     # the weak figure -- every GPU a 64k batch of its own -- is measured after
     # it and sits beside it, never in its place
-    if world > 1 and args.config == "token_ring" and not args.weak and not args.no_weak_line:
+    if args.full and world > 1 and args.config == "token_ring" and not args.weak and not args.no_weak_line:
         wa = argparse.Namespace(**vars(args))
         wa.weak = True
         wa.geometry = None if args.geometry_auto else args.geometry
         pick_geometry(wa, world)
+        wa.dump_outputs = None
         w = measure_replicas(wa, rank, world, local, dist_on, barrier, parity=False)
         if rank == 0:
             print_line["weak_line"] = {
@@ -416,7 +482,8 @@ def main():
 
 def setup_scenario(args, rank, world, local):
     """This rank's scenario (outside the timed region): the link table drawn on
-    the GPU, checked against the host StdGen draw on its first replicas."""
+    the GPU, with --full checked against the host StdGen draw on its first
+    replicas."""
     drawer = None
     if not args.host_tables and args.config != "gossip":
         from timewarp.engine import draw_link_table
@@ -425,7 +492,7 @@ def setup_scenario(args, rank, world, local):
     scn, workload = build_scenario(args, rank, world, drawer=drawer)
     setup = {"table_draw": "host" if drawer is None else "device (tw_draw_link_table)",
              "build_s": time.perf_counter() - t_setup}
-    if drawer is not None and scn.link_table is not None:
+    if args.full and drawer is not None and scn.link_table is not None:
         ref, _ = build_scenario(args, rank, world, max_replicas=TABLE_CHECK_REPLICAS)
         n_chk = ref.link_table.shape[2]
         setup["host_check_replicas"] = n_chk
@@ -436,9 +503,9 @@ def setup_scenario(args, rank, world, local):
 
 
 def measure_replicas(args, rank, world, local, dist_on, barrier, parity=True):
-    """W warm-up and K timed steps of the replica configs on this rank; the
-    parity sample (rank 0: the CPU baseline at N = 1, a smaller oracle check of
-    its own replicas at N > 1)."""
+    """W warm-up and K timed steps of the replica configs on this rank; with
+    --full the parity sample (rank 0: the CPU baseline at N = 1, a smaller
+    oracle check of its own replicas at N > 1)."""
     import torch
 
     from timewarp import dist as twd
@@ -497,7 +564,13 @@ def measure_replicas(args, rank, world, local, dist_on, barrier, parity=True):
             raise SystemExit(f"{st.replicas_error} replicas ended in an error status")
 
     res = eng.results()
-    hashes = eng.hashes()
+    parity = parity and rank == 0 and args.full and not args.no_cpu_baseline
+    # the [replicas, nodes] hashes (2 GiB for C3) are read only where they are used
+    hashes = eng.hashes() if parity or args.dump_outputs else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, res, hashes,
+                     {f: getattr(st, f) for f in ("events", "sends", "delivered", "dropped", "undeliverable",
+                                                  "replicas_error", "launches")})
     # st.* are the job's (tw_run's statistics, all-reduced by the library over
     # the ranks); this rank's own share is in its replicas' results
     m = {"scn_replicas": scn.n_replicas, "workload": workload, "setup": setup, "tie": tie,
@@ -511,7 +584,7 @@ def measure_replicas(args, rank, world, local, dist_on, barrier, parity=True):
     m["value"] = events / m["max_elapsed"]
     m["ms_per_step"] = m["max_elapsed"] * 1e3 / args.steps
     eng.close()
-    if rank == 0 and parity and not args.no_cpu_baseline:
+    if parity:
         if world == 1:  # the CPU baseline: rank 0 at N=1 only; its results double as the parity sample
             cb, ok, n = cpu_baseline(scn, res, hashes, args.cpu_seconds)
             m["cpu_baseline"] = cb
@@ -591,7 +664,7 @@ def replica_line(args, world, m):
     per["arrivals_frac"] = arrivals / max(1, per["events"])
     out["events_breakdown"] = per
     mt = (measured_traffic(args, launches / args.steps, m["loc_events"] / args.steps, geometry == "lpb")
-          if world == 1 else None)
+          if args.full and world == 1 else None)
     if mt:
         out["roofline"].update(mt)
     if "cpu_baseline" in m:

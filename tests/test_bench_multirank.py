@@ -116,11 +116,81 @@ def _worker(rank, world, port, out_path, argv):
             f.write(buf.getvalue())
 
 
+def test_bench_plain_run_and_dump(tmp_path, oracle_mod):
+    """A plain run (no --full) at N = 1: the line keeps its headline keys and
+    carries nothing of the oracle or the host table check; --dump-outputs
+    writes the last step's results and hashes as float64, the same files for
+    the same arguments."""
+    from timewarp import scenarios
+
+    lines, dumps = [], []
+    for i in range(2):
+        out, d = str(tmp_path / f"line{i}.txt"), tmp_path / f"dump{i}"
+        argv = ["--gpus", "1", "--config", "token_ring", "--replicas", "8", "--nodes", "8", "--duration-s", "5",
+                "--host-tables", "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)]
+        mp.spawn(_worker, args=(1, _free_port(), out, argv), nprocs=1, join=True)
+        lines.append([ln for ln in open(out).read().splitlines() if ln.startswith("{")])
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    assert len(lines[0]) == 1
+    line = json.loads(lines[0][0])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["unit"] == "events/s" and line["higher_is_better"] is True and line["dtype"] == "int64"
+    assert line["ms_per_step"] > 0 and line["value"] > 0 and "token-ring" in line["metric"]
+    for k in ("cpu_baseline", "parity_sample", "weak_line"):
+        assert k not in line
+    assert "host_check_equal" not in line["setup"] and "traffic_source" not in line["roofline"]
+    scn = scenarios.token_ring(n_nodes=8, n_replicas=8, launch_duration=5_000_000, drop_log2=10)
+    ores, ohashes = oracle_mod.run_batch(scn, threads=4)
+    a, b = dumps
+    assert set(a) == set(b) and {"results.npy", "hashes.npy", "hash_fold.npy", "stats.npy"} <= set(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name in a:
+        assert a[name].dtype == np.float64 and np.array_equal(a[name], b[name]), name
+    assert np.array_equal(a["results_replicas.npy"], np.arange(8))
+    for j, f in enumerate(("final_t", "events", "delivered", "dropped", "undeliverable", "status", "main_exc",
+                           "threads")):
+        assert np.array_equal(a["results.npy"][:, j], ores[f].astype(np.float64)), f
+    h = (a["hashes.npy"][..., 0].astype(np.uint64) << np.uint64(32)) | a["hashes.npy"][..., 1].astype(np.uint64)
+    assert np.array_equal(h, ohashes)
+    fold = (a["hash_fold.npy"][:, 0].astype(np.uint64) << np.uint64(32)) | a["hash_fold.npy"][:, 1].astype(np.uint64)
+    assert np.array_equal(fold, ohashes.sum(axis=1, dtype=np.uint64))
+
+
+def test_bench_dump_samples_large_outputs(tmp_path):
+    """dump_outputs keeps a fixed seeded sample of a batch whose hashes pass
+    its cap: the same rows every time, the fold over every replica's hashes."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    from timewarp.abi import RESULT_DTYPE
+
+    R, N = 3000, 1025
+    assert R * N > bench.DUMP_MAX_HASHES
+    rng = np.random.default_rng(1)
+    res = np.zeros(R, RESULT_DTYPE)
+    res["events"] = rng.integers(0, 1 << 40, R)
+    hashes = rng.integers(0, 1 << 63, (R, N)).astype(np.uint64) * np.uint64(2) + np.uint64(1)
+    for i in range(2):
+        bench.dump_outputs(str(tmp_path / str(i)), 0, 1, res, hashes, {"events": 7, "launches": 1})
+    a, b = ({f.name: np.load(f) for f in sorted((tmp_path / str(i)).iterdir())} for i in range(2))
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    rows = a["hashes_replicas.npy"].astype(np.int64)
+    assert rows.size == bench.DUMP_MAX_HASHES // N and np.all(np.diff(rows) > 0)
+    h = (a["hashes.npy"][..., 0].astype(np.uint64) << np.uint64(32)) | a["hashes.npy"][..., 1].astype(np.uint64)
+    assert np.array_equal(h, hashes[rows])
+    assert a["results.npy"].shape == (R, len(bench.DUMP_FIELDS))
+    assert np.array_equal(a["results.npy"][:, 1], res["events"].astype(np.float64))
+    fold = (a["hash_fold.npy"][:, 0].astype(np.uint64) << np.uint64(32)) | a["hash_fold.npy"][:, 1].astype(np.uint64)
+    assert np.array_equal(fold, hashes.sum(axis=1, dtype=np.uint64))
+
+
 @pytest.mark.parametrize("weak", [False, True])
 def test_bench_two_ranks(tmp_path, oracle_mod, weak):
     out = str(tmp_path / "line.txt")
     argv = ["--config", "token_ring", "--replicas", "8", "--nodes", "8", "--duration-s", "5", "--host-tables",
-            "--steps", "1", "--warmup", "0", "--cpu-seconds", "1"] + (["--weak"] if weak else [])
+            "--steps", "1", "--warmup", "0", "--cpu-seconds", "1", "--full"] + (["--weak"] if weak else [])
     mp.spawn(_worker, args=(2, _free_port(), out, argv), nprocs=2, join=True)
     lines = [ln for ln in open(out).read().splitlines() if ln.startswith("{")]
     assert len(lines) == 1

@@ -28,22 +28,22 @@ for s in "$@"; do
     stats_c4) step stats_c4 300 env TW_LIB=$PWD/time-warp_amd/lib/libtimewarp_stats.so python -u tools/stats_probe.py gossip ;;
     stats_c5) step stats_c5 400 env TW_LIB=$PWD/time-warp_amd/lib/libtimewarp_stats.so python -u tools/stats_probe.py hotspot 4096 256 ;;
     probe2) step probe2 300 env TW_LIB=$PWD/time-warp_amd/lib/libtimewarp_prof2.so python tools/kernel_probe.py 65536 4096 ;;
-    bench)  step bench 500 python bench.py ;;
+    bench)  step bench 500 python bench.py --full ;;
     tie_c3) step tie_c3 400 python -u tools/ab_probe.py token_ring 65536 auto tie=fifo tie=forkfirst ;;
     tie_c2) step tie_c2 400 python -u tools/ab_probe.py ping_pong 1048576 auto tie=fifo tie=forkfirst ;;
     tie_c3_8k) step tie_c3_8k 400 python -u tools/ab_probe.py token_ring 8192 narrow tie=fifo tie=forkfirst ;;
     benchq) step benchq 300 python bench.py --steps 2 --no-cpu-baseline ;;
-    bench_c2) step bench_c2 400 python bench.py --config ping_pong ;;
-    bench_c4) step bench_c4 500 python bench.py --config gossip ;;
+    bench_c2) step bench_c2 400 python bench.py --full --config ping_pong ;;
+    bench_c4) step bench_c4 500 python bench.py --full --config gossip ;;
     benchq_c4) step benchq_c4 300 python bench.py --config gossip --steps 2 --warmup 1 --no-cpu-baseline ;;
     benchq_c4h) step benchq_c4h 300 python bench.py --config gossip --steps 2 --warmup 1 --no-cpu-baseline --host-windows ;;
     prof_c4) step prof_c4 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_c4 -o run -- python3 bench.py --config gossip --steps 2 --warmup 1 --no-cpu-baseline ;;
     prof_c3) step prof_c3 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_c3 -o run -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline ;;
     gossip) step gossip 400 python -u -m pytest tests/test_gpu_gossip.py -q -m gpu -x --timeout 120 --timeout-method thread ;;
-    bench_msg) step bench_msg 500 python bench.py --duration-s 24576 --drop-log2 16 --steps 2 --warmup 1 ;;
+    bench_msg) step bench_msg 500 python bench.py --full --duration-s 24576 --drop-log2 16 --steps 2 --warmup 1 ;;
     pmct_msg) PMC_SET=traffic bash tools/pmc_passes.sh gpurun_out/pmct_msg$SFX --duration-s 24576 --drop-log2 16 > gpurun_out/pmct_msg$SFX.log 2>&1; rc=$?; echo "pmct_msg=$rc"; [ $rc -eq 0 ] || exit $rc ;;
     pmc_full) bash tools/pmc.sh gpurun_out/pmc_full > gpurun_out/pmc_full.log 2>&1; rc=$?; echo "pmc_full=$rc"; [ $rc -eq 0 ] || exit $rc ;;
-    bench_c5) step bench_c5 400 python bench.py --config hotspot ;;
+    bench_c5) step bench_c5 400 python bench.py --full --config hotspot ;;
     benchq_c5) step benchq_c5 400 python bench.py --config hotspot --steps 2 --warmup 1 --no-cpu-baseline ;;
     benchq_c3_8k) step benchq_c3_8k 300 python bench.py --replicas 8192 --steps 2 --warmup 1 --no-cpu-baseline ;;
     benchq_c2) step benchq_c2 300 python bench.py --config ping_pong --steps 2 --warmup 1 --no-cpu-baseline ;;
@@ -75,7 +75,7 @@ for s in "$@"; do
     stats_c5_lpb) step stats_c5_lpb 400 env TW_LIB=$PWD/time-warp_amd/lib/libtimewarp_stats.so python -u tools/stats_probe.py lpb_hotspot 4096 256 ;;
     prof_c5) step prof_c5 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_c5 -o run -- python3 bench.py --config hotspot --steps 1 --warmup 0 --no-cpu-baseline ;;
     prof_c3_8k_lpb) step prof_c3_8k_lpb 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_c3_8k_lpb -o run -- python3 bench.py --replicas 8192 --geometry lpb --steps 1 --warmup 0 --no-cpu-baseline ;;
-    bench_c3_8k) step bench_c3_8k 400 python bench.py --replicas 8192 ;;
+    bench_c3_8k) step bench_c3_8k 400 python bench.py --full --replicas 8192 ;;
     benchq_c3_32k) step benchq_c3_32k 300 python bench.py --replicas 32768 --steps 2 --warmup 1 --no-cpu-baseline ;;
     benchq_c3_16k) step benchq_c3_16k 300 python bench.py --replicas 16384 --steps 2 --warmup 1 --no-cpu-baseline ;;
     benchq_c3_32k_lpb) step benchq_c3_32k_lpb 400 python bench.py --replicas 32768 --geometry lpb --steps 1 --warmup 1 --no-cpu-baseline ;;
