@@ -374,6 +374,74 @@ int tw_set_trace(tw_ctx* ctx, uint32_t cap);
  * stores the number emitted (possibly more than were kept) in *n_emitted. */
 int tw_read_trace(tw_ctx* ctx, uint32_t replica, tw_trace_rec* out, size_t cap, uint64_t* n_emitted);
 
+/* ------------------------------------------------ measures joined on the GPU
+ * The LogReader's join (bench/Network/LogReader/Main.hs:85-119: the four
+ * measure events of a message id folded into one measures.csv row) for every
+ * replica of the batch at once, reduced on the device to the distribution of
+ * one latency t(tag_to) - t(tag_from): counts, min / max / sum and a histogram.
+ * Only the csv / ODS rendering of single replicas stays on the host
+ * (tw_read_trace).
+ *
+ * A replica's records are the kept ones, the first min(emitted, trace cap).
+ * A replica that emitted more than the cap is *truncated*: it adds 1 to
+ * `truncated` and nothing else.  Within a replica the records whose tag is
+ * tag_from or tag_to are grouped by `val` (the full int64: negative ids, 0 and
+ * INT64_MAX are legal); with cf / ct the number of tag_from / tag_to records
+ * of an id, the id is exactly one of
+ *   repeated   cf > 1 or ct > 1 (LogReader's uniqMap: no row);
+ *   pair       cf == ct == 1, latency d = t_to - t_from (may be negative);
+ *   open_from  cf == 1, ct == 0 (the csv's "-");
+ *   open_to    ct == 1, cf == 0.
+ * A pair with d < lo_us counts in `underflow`; otherwise i = (d - lo_us) /
+ * bin_us, `overflow` when i >= n_bins, else hist[i]++.  hist, underflow and
+ * overflow are batch-wide only; the per-replica entries carry the counts and
+ * min / max / sum.  `total` is the sum of the per-replica entries with the min
+ * of their mins and the max of their maxes. */
+typedef struct tw_measure_spec {
+    uint32_t tag_from, tag_to;  /* TRACE immediates, must differ */
+    uint32_t n_bins;            /* 1 .. TW_MEASURE_MAX_BINS */
+    uint32_t reserved;          /* 0 */
+    int64_t  lo_us;             /* histogram origin (may be negative) */
+    int64_t  bin_us;            /* bin width, >= 1 */
+} tw_measure_spec;
+
+typedef struct tw_measure_out {
+    uint64_t pairs;      /* ids with exactly one tag_from and one tag_to record */
+    uint64_t open_from;  /* exactly one tag_from, no tag_to  (measures.csv "-") */
+    uint64_t open_to;    /* exactly one tag_to, no tag_from */
+    uint64_t repeated;   /* ids with tag_from or tag_to more than once: no row (uniqMap) */
+    uint64_t truncated;  /* replicas that emitted more records than the trace cap:
+                            they contribute to nothing else */
+    uint64_t underflow, overflow;  /* pairs left of lo_us / right of the last bin */
+    int64_t  min_us, max_us;       /* INT64_MAX / INT64_MIN when pairs == 0 */
+    int64_t  sum_us;               /* two's-complement sum of the pairs' latencies */
+} tw_measure_out;
+
+/* tag_from + tag_to records one replica may hold: the join sorts a replica's
+ * keys in one workgroup's LDS (there is no global-memory sort path). */
+#define TW_MEASURE_MAX_KEYS 2048u
+#define TW_MEASURE_MAX_BINS 4096u
+
+/* Blocking, stream-ordered after the last tw_run; changes no state (results,
+ * hashes and traces read afterwards are what they were) and may be called
+ * repeatedly with different specs.  hist: n_bins counters or NULL; per_replica:
+ * n entries in replica order or NULL (n = 0, or the context's replica count).
+ * TW_ERR_STATE when nothing is loaded or tracing is off; TW_ERR_INVALID for an
+ * LP / LPB context (as tw_set_trace: TRACE records exist in replica mode only),
+ * for a bad spec (tag_from == tag_to, n_bins == 0 or > TW_MEASURE_MAX_BINS,
+ * bin_us < 1, reserved != 0), for another n, and when some non-truncated
+ * replica holds more than TW_MEASURE_MAX_KEYS matching records -- decided on
+ * the device before the join runs; no output is written then.  A context over
+ * several devices runs every shard and combines on the host.  A rank context
+ * (tw_create_rank) measures this rank's replicas only: there is no job-wide
+ * reduction over ranks. */
+int tw_measure(tw_ctx* ctx, const tw_measure_spec* spec, tw_measure_out* total,
+               uint64_t* hist /* [n_bins] or NULL */,
+               tw_measure_out* per_replica /* [n] or NULL */, size_t n);
+/* Device time (ms, HIP events) of the kernels of the last tw_measure: the
+ * slowest shard's. */
+int tw_measure_ms(tw_ctx* ctx, double* kernel_ms);
+
 /* Tie-order audit: run every replica (as tw_run with t_end_us / max_events)
  * under each probe order p in 1..probes (TW_TIE_LIFO, TW_TIE_SCRAMBLE), then
  * under the canonical order, and set tie_flags bit p of every replica whose

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/timewarp.h"
+#include "measure_combine.hpp"
 #include "shard.hpp"
 #include "tw_dev.hpp"
 
@@ -79,6 +80,7 @@ struct tw_ctx {
     // context was made (0: off), and the checked RCCL calls made since
     long test_fail_at = 0;
     std::atomic<long> test_calls{0};
+    double measure_ms = 0.0;  // kernels of the last tw_measure (tw_measure_ms)
 };
 
 namespace {
@@ -603,6 +605,51 @@ int tw_read_trace(tw_ctx* c, uint32_t replica, tw_trace_rec* out, size_t cap, ui
         if (replica >= b0) return sh_read_trace(c->sh[i], replica - b0, out, cap, n_emitted);
     }
     return TW_ERR_INVALID;
+}
+
+// Every shard measures its own replicas; the host folds the shards' outputs
+// (measure_combine.hpp) into temporaries and hands them out only when every
+// shard succeeded, so a failing call leaves the caller's buffers untouched.
+int tw_measure(tw_ctx* c, const tw_measure_spec* spec, tw_measure_out* total, uint64_t* hist,
+               tw_measure_out* per_replica, size_t n) {
+    if (!c || !spec) return TW_ERR_INVALID;
+    for (tw_shard* s : c->sh) {
+        int rc = sh_measure_state(s);
+        if (rc) return rc;
+    }
+    if (!measure_spec_ok(spec)) return TW_ERR_INVALID;
+    if (n == 0) per_replica = nullptr;
+    if (per_replica && n != local_replicas(c)) return TW_ERR_INVALID;
+    tw_measure_out tot;
+    measure_empty(&tot);
+    std::vector<uint64_t> h(spec->n_bins, 0), sh_h(spec->n_bins);
+    std::vector<tw_measure_out> per(per_replica ? n : 0), sh_per;
+    double ms = 0.0;
+    size_t off = 0;
+    for (tw_shard* s : c->sh) {
+        const size_t k = sh_replicas(s);
+        tw_measure_out st;
+        double sms = 0.0;
+        if (per_replica) sh_per.resize(k);
+        int rc = sh_measure(s, spec, &st, sh_h.data(), per_replica ? sh_per.data() : nullptr, &sms);
+        if (rc) return rc;
+        if (!measure_combine(&tot, h.data(), spec->n_bins, per_replica ? per.data() : nullptr, n, &st, sh_h.data(),
+                             per_replica ? sh_per.data() : nullptr, off, k))
+            return TW_ERR_INVALID;
+        ms = sms > ms ? sms : ms;
+        off += k;
+    }
+    if (total) *total = tot;
+    if (hist) std::memcpy(hist, h.data(), (size_t)spec->n_bins * 8);
+    if (per_replica) std::memcpy(per_replica, per.data(), n * sizeof(tw_measure_out));
+    c->measure_ms = ms;
+    return TW_OK;
+}
+
+int tw_measure_ms(tw_ctx* c, double* kernel_ms) {
+    if (!c || !kernel_ms) return TW_ERR_INVALID;
+    *kernel_ms = c->measure_ms;
+    return TW_OK;
 }
 
 int tw_set_counter_base(tw_ctx* c, uint32_t seq0, uint32_t tid0) {

@@ -1669,6 +1669,23 @@ int sh_read_trace(tw_shard* c, uint32_t replica, tw_trace_rec* out, size_t cap, 
     return TW_OK;
 }
 
+int sh_measure_state(tw_shard* c) {
+    if (!c) return TW_ERR_INVALID;
+    if (!c->loaded) return TW_ERR_STATE;
+    if (c->lp) return TW_ERR_INVALID;  // as sh_set_trace: TRACE records exist in replica mode only
+    if (!c->d.trace || !c->d.trace_cap) return TW_ERR_STATE;
+    return TW_OK;
+}
+
+int sh_measure(tw_shard* c, const tw_measure_spec* spec, tw_measure_out* total, uint64_t* hist, tw_measure_out* per,
+               double* kernel_ms) {
+    int rc = sh_measure_state(c);
+    if (rc) return rc;
+    const Dev& d = c->d;
+    return measure_run(c->device, c->stream, d.trace, d.scal + (size_t)SC_TRACE_N * d.R, d.R, d.trace_cap, spec,
+                       total, hist, per, kernel_ms);
+}
+
 int sh_last_launch_ms(tw_shard* c, double* out, size_t cap) {
     if (!c || !out) return TW_ERR_INVALID;
     size_t n = c->launch_ms.size() < cap ? c->launch_ms.size() : cap;

@@ -34,6 +34,18 @@ TW_HIDDEN int sh_set_counter_base(tw_shard* c, uint32_t seq0, uint32_t tid0);
 TW_HIDDEN int sh_set_tie_mode(tw_shard* c, uint32_t mode);
 TW_HIDDEN int sh_set_trace(tw_shard* c, uint32_t cap);
 TW_HIDDEN int sh_read_trace(tw_shard* c, uint32_t replica, tw_trace_rec* out, size_t cap, uint64_t* n_emitted);
+// tw_measure on one shard: sh_measure_state is its state check alone
+// (TW_ERR_STATE nothing loaded / tracing off, TW_ERR_INVALID LP / LPB);
+// sh_measure writes total, hist[n_bins] (or NULL), per[sh_replicas] (or NULL)
+// and the kernels' device time only on success
+TW_HIDDEN int sh_measure_state(tw_shard* c);
+TW_HIDDEN int sh_measure(tw_shard* c, const tw_measure_spec* spec, tw_measure_out* total, uint64_t* hist,
+                         tw_measure_out* per, double* kernel_ms);
+// the measure pass itself (measure.hip) over a shard's trace buffer
+// ([cap][R][2] quads) and its per-replica emitted counts
+TW_HIDDEN int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64_t* emitted, uint32_t R,
+                          uint32_t cap, const tw_measure_spec* spec, tw_measure_out* total, uint64_t* hist,
+                          tw_measure_out* per, double* kernel_ms);
 TW_HIDDEN int sh_last_launch_ms(tw_shard* c, double* out, size_t cap);
 TW_HIDDEN int sh_prof_read(tw_shard* c, unsigned long long* out, size_t cap, int reset);
 // shape of what a shard holds: replicas its results cover (batched LP: the

@@ -98,6 +98,37 @@ class TwTableDraw(C.Structure):
     ]
 
 
+class TwMeasureSpec(C.Structure):
+    """tw_measure_spec: the two TRACE tags to join and the histogram's shape."""
+    _fields_ = [
+        ("tag_from", C.c_uint32),
+        ("tag_to", C.c_uint32),
+        ("n_bins", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("lo_us", C.c_int64),
+        ("bin_us", C.c_int64),
+    ]
+
+
+class TwMeasureOut(C.Structure):
+    """tw_measure_out: class counts and min / max / sum of one latency."""
+    _fields_ = [
+        ("pairs", C.c_uint64),
+        ("open_from", C.c_uint64),
+        ("open_to", C.c_uint64),
+        ("repeated", C.c_uint64),
+        ("truncated", C.c_uint64),
+        ("underflow", C.c_uint64),
+        ("overflow", C.c_uint64),
+        ("min_us", C.c_int64),
+        ("max_us", C.c_int64),
+        ("sum_us", C.c_int64),
+    ]
+
+
+MEASURE_MAX_KEYS = 2048   # TW_MEASURE_MAX_KEYS
+MEASURE_MAX_BINS = 4096   # TW_MEASURE_MAX_BINS
+
 RESULT_FIELDS = ["final_t", "events", "delivered", "dropped", "undeliverable", "status", "main_exc", "threads"]
 
 # numpy dtype with the same layout as tw_replica_result (for bulk reads)
@@ -109,4 +140,8 @@ RESULT_DTYPE = _np.dtype([
     ("main_exc", _np.uint32), ("threads", _np.uint64), ("tie_flags", _np.uint32), ("reserved", _np.uint32),
 ])
 assert RESULT_DTYPE.itemsize == C.sizeof(TwReplicaResult)
+
+# numpy dtype with the same layout as tw_measure_out (tw_measure's per-replica array)
+MEASURE_DTYPE = _np.dtype([(f, _np.int64 if t is C.c_int64 else _np.uint64) for f, t in TwMeasureOut._fields_])
+assert MEASURE_DTYPE.itemsize == C.sizeof(TwMeasureOut)
 assert isa.ABI_VERSION == 4

@@ -16,7 +16,8 @@ from typing import Optional
 
 import numpy as np
 
-from .abi import RESULT_DTYPE, TwLpState, TwStats, TwTableDraw
+from .abi import (MEASURE_DTYPE, RESULT_DTYPE, TwLpState, TwMeasureOut, TwMeasureSpec, TwStats,
+                  TwTableDraw)
 from .scenario import Scenario
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,7 +31,7 @@ EXPORTS = ["tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_ru
            "tw_set_trace", "tw_read_trace", "tw_tie_audit", "tw_set_counter_base", "tw_geometry",
            "tw_set_stream", "tw_lp_exchange_setup", "tw_lp_loop_begin", "tw_lp_tick", "tw_lp_tick_import",
            "tw_lp_tick_end", "tw_lp_progress", "tw_lp_run_windows", "tw_lpb_load", "tw_lpb_windows",
-           "tw_draw_link_table", "tw_lpb_batch"]
+           "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms"]
 GEOMETRIES = ("dense", "sparse", "half", "wave", "lp", "narrow", "lpb", "compact")  # TW_GEO_* order
 
 # tw_trace_rec (include/timewarp.h)
@@ -106,12 +107,15 @@ def load_library(path: Optional[str] = None):
     lib.tw_lpb_windows.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.tw_lpb_batch.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.tw_draw_link_table.argtypes = [C.c_int, C.POINTER(TwTableDraw), C.c_void_p]
+    lib.tw_measure.argtypes = [C.c_void_p, C.POINTER(TwMeasureSpec), C.POINTER(TwMeasureOut), C.c_void_p, C.c_void_p,
+                               C.c_size_t]
+    lib.tw_measure_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     for name in ("tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_run", "tw_set_tie_mode", "tw_load", "tw_reset", "tw_run", "tw_read_results", "tw_read_hashes", "tw_read_final",
                  "tw_last_launch_ms", "tw_lp_load", "tw_lp_window", "tw_lp_take_outbox", "tw_lp_inject",
                  "tw_lp_results", "tw_set_trace", "tw_read_trace", "tw_tie_audit", "tw_set_counter_base",
                  "tw_geometry", "tw_set_stream", "tw_lp_exchange_setup", "tw_lp_loop_begin", "tw_lp_tick",
                  "tw_lp_tick_import", "tw_lp_tick_end", "tw_lp_progress", "tw_lp_run_windows", "tw_lpb_load",
-                 "tw_lpb_windows", "tw_draw_link_table", "tw_lpb_batch"):
+                 "tw_lpb_windows", "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms"):
         getattr(lib, name).restype = C.c_int
     if path is None:
         _lib = lib
@@ -142,7 +146,9 @@ def draw_link_table(n_replicas: int, drawn, lo, hi, link_depth: int = 1, drop_lo
 def _check(rc: int, what: str):
     if rc < 0:
         msg = load_library().tw_strerror(rc).decode()
-        raise EngineError(f"{what} failed: {rc} ({msg})")
+        err = EngineError(f"{what} failed: {rc} ({msg})")
+        err.code = rc  # the tw_status
+        raise err
 
 
 @dataclass
@@ -357,6 +363,30 @@ class Engine:
         n = C.c_uint64()
         _check(self.lib.tw_read_trace(self.ctx, int(replica), buf.ctypes.data, cap, C.byref(n)), "tw_read_trace")
         return buf[:min(int(n.value), cap, getattr(self, "_trace_cap", 0))].copy(), int(n.value)
+
+    def measure(self, tag_from: int, tag_to: int, lo_us: int = 0, bin_us: int = 1, n_bins: int = 1,
+                per_replica: bool = False):
+        """The batch's latency t(tag_to) - t(tag_from), joined per message id
+        and reduced on the GPU (tw_measure): (total, hist, per_replica) with
+        `total` a dict of tw_measure_out's fields, `hist` the n_bins uint64
+        counters of bins [lo_us + i * bin_us, lo_us + (i + 1) * bin_us), and
+        per_replica a MEASURE_DTYPE array in replica order (or None).  Needs
+        set_trace; reads only what the last run recorded."""
+        spec = TwMeasureSpec(tag_from=int(tag_from), tag_to=int(tag_to), n_bins=int(n_bins), reserved=0,
+                             lo_us=int(lo_us), bin_us=int(bin_us))
+        tot = TwMeasureOut()
+        hist = np.zeros(max(int(n_bins), 0), np.uint64)
+        n = self.scn.n_replicas if (per_replica and self.scn is not None) else 0
+        per = np.zeros(n, MEASURE_DTYPE) if per_replica else None
+        _check(self.lib.tw_measure(self.ctx, C.byref(spec), C.byref(tot), hist.ctypes.data if hist.size else None,
+                                   per.ctypes.data if n else None, n), "tw_measure")
+        return {f: int(getattr(tot, f)) for f, _ in TwMeasureOut._fields_}, hist, per
+
+    def measure_ms(self) -> float:
+        """Device time (ms) of the last measure()'s kernels."""
+        v = C.c_double()
+        _check(self.lib.tw_measure_ms(self.ctx, C.byref(v)), "tw_measure_ms")
+        return float(v.value)
 
     def launch_ms(self) -> np.ndarray:
         buf = np.zeros(1 << 16, np.float64)

@@ -59,6 +59,89 @@ def format_measures_csv(measures: Dict[int, Dict[str, int]], size: int = 0) -> s
     return "".join(lines)
 
 
+# ------------------------------------------------ host restatement of tw_measure
+# (include/timewarp.h).  The yardstick of the GPU pass: plain Python over
+# (t, node, tag, val) tuples, no engine call.
+_I64_MAX, _I64_MIN = (1 << 63) - 1, -(1 << 63)
+
+
+def _wrap64(x: int) -> int:
+    """x as a two's-complement int64."""
+    return ((int(x) + (1 << 63)) & ((1 << 64) - 1)) - (1 << 63)
+
+
+def pair_latencies(records: Iterable[Tuple[int, int, int, int]], tag_from: int, tag_to: int):
+    """One replica's join of `tag_from` and `tag_to` records on equal `val`.
+    Returns (latencies, counts): the latency t_to - t_from of every id with
+    exactly one record of each tag (in ascending id order), and the class
+    counts {"pairs", "open_from", "open_to", "repeated"}; an id with either tag
+    more than once is `repeated` and has no latency (LogReader's uniqMap)."""
+    if tag_from == tag_to:
+        raise ValueError("tag_from and tag_to must differ")
+    ids: Dict[int, Tuple[list, list]] = {}
+    for t, _node, tag, val in records:
+        if int(tag) == tag_from:
+            ids.setdefault(int(val), ([], []))[0].append(int(t))
+        elif int(tag) == tag_to:
+            ids.setdefault(int(val), ([], []))[1].append(int(t))
+    counts = {"pairs": 0, "open_from": 0, "open_to": 0, "repeated": 0}
+    lat = []
+    for val in sorted(ids):
+        tf, tt = ids[val]
+        if len(tf) > 1 or len(tt) > 1:
+            counts["repeated"] += 1
+        elif tf and tt:
+            counts["pairs"] += 1
+            lat.append(_wrap64(tt[0] - tf[0]))
+        elif tf:
+            counts["open_from"] += 1
+        else:
+            counts["open_to"] += 1
+    return lat, counts
+
+
+def measure_reference(per_replica_records, emitted, cap: int, spec: dict):
+    """tw_measure restated on the host.  per_replica_records[r]: replica r's
+    (t, node, tag, val) tuples in execution order (at least its first
+    min(emitted[r], cap)); emitted[r]: the records it emitted; cap: the trace
+    cap; spec: {"tag_from", "tag_to", "lo_us", "bin_us", "n_bins"}.  Returns
+    (total dict, hist uint64[n_bins], per-replica MEASURE_DTYPE array)."""
+    import numpy as np
+
+    from .abi import MEASURE_DTYPE
+
+    lo, width, n_bins = int(spec.get("lo_us", 0)), int(spec.get("bin_us", 1)), int(spec.get("n_bins", 1))
+    if n_bins < 1 or width < 1:
+        raise ValueError("n_bins and bin_us must be >= 1")
+    per = np.zeros(len(per_replica_records), MEASURE_DTYPE)
+    hist = [0] * n_bins
+    under = over = 0
+    for r, recs in enumerate(per_replica_records):
+        per[r]["min_us"], per[r]["max_us"] = _I64_MAX, _I64_MIN
+        if int(emitted[r]) > cap:
+            per[r]["truncated"] = 1
+            continue
+        lat, counts = pair_latencies(list(recs)[:int(emitted[r])], int(spec["tag_from"]), int(spec["tag_to"]))
+        for f, v in counts.items():
+            per[r][f] = v
+        if lat:
+            per[r]["min_us"], per[r]["max_us"] = min(lat), max(lat)
+        per[r]["sum_us"] = _wrap64(sum(lat))
+        for d in lat:
+            if d < lo:
+                under += 1
+            elif (d - lo) // width >= n_bins:
+                over += 1
+            else:
+                hist[(d - lo) // width] += 1
+    total = {f: int(per[f].sum()) for f in ("pairs", "open_from", "open_to", "repeated", "truncated")}
+    total["underflow"], total["overflow"] = under, over
+    total["min_us"] = int(per["min_us"].min()) if len(per) else _I64_MAX
+    total["max_us"] = int(per["max_us"].max()) if len(per) else _I64_MIN
+    total["sum_us"] = _wrap64(sum(int(x) for x in per["sum_us"]))
+    return total, np.array(hist, dtype=np.uint64), per
+
+
 def trace_tuples(recs) -> list:
     """Engine.trace records (TRACE_DTYPE) or oracle traces -> (t, node, tag, val) tuples."""
     if hasattr(recs, "dtype"):

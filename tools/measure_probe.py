@@ -1,0 +1,92 @@
+"""tw_measure against the host path on a hotspot batch: the round-trip latency
+TAG_PING_SENT -> TAG_PONG of senders x messages x replicas, joined and reduced
+on the GPU (Engine.measure), and the same join done the old way -- one
+tw_read_trace per replica plus measures_from_trace in the interpreter -- timed
+on a sample of replicas and scaled to the batch (an extrapolation).  The
+device's per-replica entries of the sample must equal measure_reference.
+
+usage: python tools/measure_probe.py [--senders 8] [--msgs 40] [--replicas 65536]
+                                     [--host-sample 256] [--out profiles/measure/probe.log]"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "time-warp_amd"))
+from timewarp import scenarios  # noqa: E402
+from timewarp.engine import Engine, draw_link_table  # noqa: E402
+from timewarp.measures import measure_reference, measures_from_trace, trace_tuples  # noqa: E402
+from timewarp.scenarios import TAG_PING_SENT, TAG_PONG  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--senders", type=int, default=8)
+ap.add_argument("--msgs", type=int, default=40)
+ap.add_argument("--replicas", type=int, default=65536)
+ap.add_argument("--host-sample", type=int, default=256)
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "measure", "probe.log"))
+a = ap.parse_args()
+
+S, M, R = a.senders, a.msgs, a.replicas
+cap = 4 * S * M  # four measure events per message
+spec = dict(tag_from=TAG_PING_SENT, tag_to=TAG_PONG, lo_us=2000, bin_us=250, n_bins=40)
+lines = []
+
+
+def say(s):
+    print(s, flush=True)
+    lines.append(s)
+
+
+scn = scenarios.hotspot(n_senders=S, n_replicas=R, msg_num=M, drawer=draw_link_table)
+with Engine(0) as e:
+    e.load(scn).set_trace(cap).reset()
+    st = e.run()
+    say(f"hotspot {S} senders x {M} messages x {R} replicas, geometry {e.geometry()}: {st.events} events, "
+        f"event kernels {st.kernel_ms:.1f} ms, tw_run wall {st.wall_ms:.1f} ms; {cap * R} trace records "
+        f"({cap * R * 32 / 2**30:.2f} GiB)")
+    # device path: every replica, with the per-replica array
+    for i in range(3):
+        t0 = time.perf_counter()
+        total, hist, per = e.measure(spec["tag_from"], spec["tag_to"], spec["lo_us"], spec["bin_us"], spec["n_bins"],
+                                     per_replica=True)
+        wall = (time.perf_counter() - t0) * 1e3
+        say(f"tw_measure call {i}: wall {wall:.2f} ms, kernels {e.measure_ms():.3f} ms (HIP events)")
+    t0 = time.perf_counter()
+    e.measure(spec["tag_from"], spec["tag_to"], spec["lo_us"], spec["bin_us"], spec["n_bins"])
+    say(f"tw_measure without per_replica: wall {(time.perf_counter() - t0) * 1e3:.2f} ms, "
+        f"kernels {e.measure_ms():.3f} ms")
+    say(f"total {total}")
+    say(f"hist[{spec['lo_us']} + i * {spec['bin_us']} us] {hist.tolist()}")
+    assert total["pairs"] == S * M * R and total["truncated"] == 0, total
+
+    # host path on a sample: Engine.trace + measures_from_trace per replica
+    n = min(a.host_sample, R)
+    sample = np.linspace(0, R - 1, n).astype(np.int64)
+    recs, emitted = [], []
+    t0 = time.perf_counter()
+    for r in sample:
+        rr, em = e.trace(int(r), cap=cap)
+        tup = trace_tuples(rr)
+        ms = measures_from_trace(tup)
+        lat = [m["PongReceived"] - m["PingSent"] for m in ms.values() if m and "PongReceived" in m and "PingSent" in m]
+        recs.append(tup)
+        emitted.append(em)
+    host = time.perf_counter() - t0
+    say(f"host path (Engine.trace + measures_from_trace) on {n} replicas: {host * 1e3:.1f} ms = "
+        f"{host / n * 1e3:.3f} ms per replica; scaled to {R} replicas (extrapolated): {host / n * R:.1f} s")
+    rtot, _rhist, rper = measure_reference(recs, emitted, cap, spec)
+    for f in per.dtype.names:
+        assert np.array_equal(per[f][sample], rper[f]), f
+    for f in ("pairs", "open_from", "open_to", "repeated", "truncated"):
+        assert int(per[f][sample].sum()) == rtot[f], f
+    assert int(per["min_us"][sample].min()) == rtot["min_us"] and int(per["max_us"][sample].max()) == rtot["max_us"]
+    assert int(per["sum_us"][sample].sum()) == rtot["sum_us"]
+    say(f"device per_replica entries of the {n} sampled replicas equal measure_reference: "
+        f"pairs {rtot['pairs']}, min {rtot['min_us']}, max {rtot['max_us']}, sum {rtot['sum_us']}")
+
+os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+with open(a.out, "w") as f:
+    f.write("\n".join(lines) + "\n")
