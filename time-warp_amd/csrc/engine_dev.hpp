@@ -62,6 +62,11 @@
 #define TW_CW_REGS 0
 #endif
 #define TW_TAIL_VMEM 9          // vector-memory ops of every iteration after the record prefetch
+#define TW_REAP_VMEM 1          // ... of a reap iteration (no lane of the wave runs a thread): the hash atomic alone
+// reap iterations (the run geometries but the sparse one): 0 builds the A/B baseline
+#ifndef TW_REAP
+#define TW_REAP 1
+#endif
 
 // LP event kernel: waves per SIMD it is built for (2: <= 256 registers, which
 // spills; 1: the AGPRs too, no scratch)
@@ -92,7 +97,7 @@
 #ifndef TW_LP_WAVES
 #define TW_LP_WAVES 2
 #endif
-#define P_COUNT 36
+#define P_COUNT 41
 #define TW_BPROF 8  // diagnostic build: tw_lp_batch's phase cycles after the two P_COUNT sets
 // Diagnostic build (-DTW_STATS, lib/libtimewarp_stats.so): per-lane event-path
 // counters summed into Dev::prof at kernel end (tools/stats_probe.py).  The
@@ -108,7 +113,11 @@ enum { K_POP, K_SUPERSEDED, K_PEEK_PF, K_PEEK_HBM, K_PUT_HBM, K_PUT_DEAD, K_PF_I
        K_NEAR_PUSH, K_RUN_PUSH, K_FAR_PUSH, K_INSN, K_CYC_POP, K_CYC_INTERP, K_CYC_TAIL,
        K_CYC_SEL, K_CYC_FETCH, K_CYC_QPOP, K_CYC_COMMIT, K_CYC_PF, K_CYC_TERM, K_CYC_STORE, K_CYC_HASH,
        K_CYC_SPAWN, K_CYC_ENQ, K_SPAWN, K_ALLOC_LD, K_ITER, K_CYC_SEND, K_CYC_DELIV, K_CYC_DUE, K_CYC_PRO,
-       K_CYC_EPI, K_CYC_IP, K_PASS };
+       K_CYC_EPI, K_CYC_IP, K_PASS,
+       // the teardown's two kinds of pop: a kill wake (its step opens with throwTo) and a victim (the popped thread
+       // died of its pending exception), each with its iterations' cycles; lane-iterations in which no lane of the
+       // wave had a thread to run
+       K_KPOP, K_VPOP, K_CYC_KIT, K_CYC_VIT, K_NORUN };
 #ifdef TW_STATS
 #define STIME(v) const uint64_t v = __builtin_amdgcn_s_memtime()
 #define STADD(i, v) (st[(i)] += (uint32_t)(v))
@@ -1122,6 +1131,10 @@ struct Lane {
     // lane then reads the staging quads, so no register stays pending on a
     // load across the merge (which made the compiler wait vmcnt(0) -- for the
     // previous iteration's store tail too -- on the common path).
+    // TAIL: the vector-memory ops the previous iteration issued after its
+    // prefetch -- TW_TAIL_VMEM, or TW_REAP_VMEM after a reap iteration (a
+    // literal per call site: the pop phase after a reap iteration is its own code)
+    template <int TAIL = TW_TAIL_VMEM>
     __device__ __forceinline__ void fetch_rec(uint32_t slot, Th& th) {
         if (slot != pf_slot) {
             STAT(K_PEEK_HBM);
@@ -1131,7 +1144,7 @@ struct Lane {
         } else {
             STAT(K_PEEK_PF);
         }
-        asm volatile("s_waitcnt vmcnt(%0) ; tw:pf" ::"n"(TW_TAIL_VMEM) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0) ; tw:pf" ::"n"(TAIL) : "memory");
         unpack(th, pfs[0], pfs[WG], pfs[2 * WG], pfs[3 * WG]);
     }
 
@@ -3044,113 +3057,80 @@ tw_run_kernel(Dev c, int64_t t_end, uint64_t max_events, uint32_t budget) {
             // cap, error) just idles through the remaining iterations, so no per-lane
             // break/continue splits the wave's control flow.
             bool alive = L.status == TW_REP_RUNNING;
+            // Reap iterations (the run geometries but the sparse one).  When no lane
+            // of the wave has a thread to run after the pop phase -- every lane is
+            // idle, popped a superseded entry, or its thread died of its pending
+            // exception: the victim sweep of C3's teardown, 8,192 pops per replica --
+            // the step and its store tail have nothing to do (the tail would send
+            // all eight stores to the sinks).  Such an iteration issues only the
+            // prefetch, the far-run commit and the hash atomic, and the pop phase
+            // after it waits for its prefetch with vmcnt(TW_REAP_VMEM).  That pop
+            // phase is a second copy of the code (engine_pop.inc, included as text
+            // with its own wait count), so each counted wait is a literal whose
+            // count holds on every path that reaches it (tools/waitcnt_audit.py).
+            // Every other kernel's loop body is the one it always had.
+            constexpr bool REAP = HR && WG >= 64 && TW_REAP;
+        #ifdef TW_STATS
+            uint64_t tl0 = 0;
+            uint32_t pkind = 0;  // this iteration's pop: 1 a victim (died of its pending exception), 2 a kill wake
+        #endif
             for (uint32_t it = 0; it < budget; ++it) {
                 if (!__builtin_amdgcn_ballot_w64(alive)) break;
-                STIME(tl0);
-                STATL(K_ITER);  // lane-iterations, idle lanes included (pops / this = lane efficiency)
                 Th th;
                 uint32_t slot = 0;
                 bool run = false;
-                // the rare cases (main's first run, quiescence, the event cap) behind one
-                // wave-uniform branch; the common path is a single divergent region
-                const bool rare = alive && (pending_main || L.live == 0 || L.d_ev >= ev_room);
-                if (__builtin_amdgcn_ballot_w64(rare)) {
-                    if (rare && pending_main) {  // runInSandbox main (TimedT.hs:237): runs at t=0, not a pop
-                        pending_main = 0;
-                        L.pf_slot = 0xFFFFFFFFu;
-                        L.fetch_rec(0, th);
-                        L.rf[0] = th.r0; L.rf[WG] = th.r1; L.rf[2 * WG] = th.r2; L.rf[3 * WG] = th.r3;
-                        L.hnode = th.w1;
-                        run = true;
-                    } else if (rare) {  // whileM_ notDone, or this launch's event cap
-                        if (!LP && L.live == 0) L.status = TW_REP_DONE;  // an LP may still receive records
-                        alive = false;
-                    }
-                }
-                bool popping = alive && !rare;
-                L.q1d = false;
-                {
-                    // PQ.minView: the min of the near root and the far sources
-                    if (L.far_dirty) L.far_min();
-                    const bool use_near = L.near_n != 0;
-                    const int64_t tn = L.nbase + (int64_t)(L.nrk >> 32);
-                    const bool use_far = L.fsrc >= 0 && (!use_near || tless(L.fmt, L.fms, tn, (uint32_t)L.nrk));
-                    const int64_t t = use_far ? L.fmt : tn;
-                    const uint32_t sq = use_far ? L.fms : (uint32_t)L.nrk;
-                    slot = use_far ? L.fmsl : (use_near ? L.nrs : 0u);
-                    STIME(ts1);
-                    STADDL(K_CYC_SEL, ts1 - tl0);
-                    // parked beyond t_end (an empty queue cannot happen while live > 0)
-                    const bool parked = popping && ((!use_near && !use_far) || t > te);
-                    alive = parked ? false : alive;
-                    popping = popping && !parked;
-                    if (popping) {
-                        {
-                            const bool due = LP && use_far && L.fsrc == 0;
-                            if (due) L.due_pop(th, slot, sq);
-                            else L.fetch_rec(slot, th);  // prefetched copy or HBM
-                            STIME(ts2);
-                            STADDL(K_CYC_FETCH, due ? 0 : ts2 - ts1);
-                            STADDL(K_CYC_DUE, due ? ts2 - ts1 : 0);
-                            if (due) {
-                            } else if (!use_far) L.near_pop();
-                            else if (L.fsrc == TW_RUNS) {
-                                // (drained: the heap walk issues loads whose values go
-                                // unused; left in flight, they made the compiler wait
-                                // vmcnt(0) -- for the record prefetch and the last
-                                // pass's stores -- at the top of every interpreter
-                                // pass of every step, tools/waitcnt_audit.py)
-                                L.far_pop();
-                                tw_vm_drain();
-                            } else L.run_pop(L.fsrc);
-                            STIME(ts3);
-                            STADDL(K_CYC_QPOP, ts3 - ts2);
-                            if (slot == L.pf_slot) L.pf_slot = 0xFFFFFFFFu;
-                            if (th.w3 != sq) {
-                                STATL(K_SUPERSEDED);  // superseded by a throwTo re-stamp
-                            } else {
-                                STATL(K_POP);
-                                // curTime .= timestamp (TimedT.hs:241-247)
-                                th.w3 = 0;
-                                --L.live;
-                                L.now = t;
-                                if (t - L.nbase > (int64_t)0x7FFFFFFF) L.near_rebase(t);
-                                L.hnode = th.w1;
-                                L.rf[0] = th.r0; L.rf[WG] = th.r1; L.rf[2 * WG] = th.r2; L.rf[3 * WG] = th.r3;
-                                // LP phantom = the deliverer's wake, already counted and hashed by the sender
-                                const bool phantom = LP && (th_flags(th) & F_PHANTOM);
-                                if (!phantom) {
-                                    L.final_t = LP ? (t > L.final_t ? t : L.final_t) : t;
-                                    ++L.d_ev;
-                                }
-                                const uint32_t exc = th_exc(th);  // asyncExceptions . at tid <<.= Nothing (:252)
-                                if (exc) {
-                                    const int64_t val = th_xval(th);
-                                    th_set_exc(th, 0);
-                                    th.xl = th.xh = 0;
-                                    L.q1d = true;
-                                    L.hacc += term0(t, TW_KIND_EXC | exc);
-                                    if (!(th_flags(th) & (F_STARTED | F_MAIN))) {  // escapes launchTimedT (:252-263)
-                                        L.status = TW_REP_ABORTED;
-                                        L.cs(CW_MAINEXC, exc);
-                                        L.put_rec(slot, th);
-                                    } else {
-                                        run = L.unwind(th, slot, exc, val);
-                                    }
-                                } else {
-                                    if (!phantom) L.hacc += term0(t, TW_KIND_RESUME | th_pc(th));
-                                    run = true;
-                                }
-                            }
+#define TW_POP_TAIL TW_TAIL_VMEM
+#include "engine_pop.inc"
+#undef TW_POP_TAIL
+                if constexpr (REAP) {
+                    Th& th_o = th;
+                    uint32_t& slot_o = slot;
+                    bool& run_o = run;
+                    while (!__builtin_amdgcn_ballot_w64(run)) {
+                        STATL(K_NORUN);
+                        alive = alive && L.status == TW_REP_RUNNING;
+                        // (the iteration counts against the launch's budget like any other.)
+                        // The launch's last iteration takes the ordinary tail below, so the
+                        // loops' exits stay the ordinary iteration's: no exit has a reap
+                        // iteration's prefetch or far-run entry in flight, however the
+                        // compiler funnels them through the outer loop's latch
+                        if (it + 1 >= budget || !__builtin_amdgcn_ballot_w64(alive)) break;
+                        ++it;
+                        STIME(tp0);
+                        L.prefetch_all(0xFFFFFFFFu);
+                        STIME(tl1);
+                        STADDL(K_CYC_PF, tl1 - tp0);
+                        STADDL(K_CYC_POP, tl1 - tl0);
+                        L.run_commit();
+                        L.hash_flush_all();
+                        STIME(tl2);
+                        STADDL(K_CYC_TAIL, tl2 - tl1);
+                        STADDL(K_CYC_VIT, pkind == 1 ? tl2 - tl0 : 0);
+                        {   // the next pop phase, into a record of its own (only the lanes
+                            // that pop write it: no lane's stale record is carried round)
+                            Th th;
+                            uint32_t slot = 0;
+                            bool run = false;
+#define TW_POP_TAIL TW_REAP_VMEM
+#include "engine_pop.inc"
+#undef TW_POP_TAIL
+                            th_o = th;
+                            slot_o = slot;
+                            run_o = run;
                         }
                     }
                 }
-                if (!popping) slot = 0u;  // main's first run is slot 0; idle lanes do not use it
+        #ifdef TW_STATS
+                if (!REAP && !__builtin_amdgcn_ballot_w64(run)) STATL(K_NORUN);
+        #endif
                 // (the compact geometry: neither -- C2's threads resume at no JMP
                 // and throw nothing, and its per-pop cost is the bound)
                 uint32_t pw = 0, n0 = 0;
                 if constexpr (RUNS) n0 = L.jump_at_pop(th, run, pw);
                 if constexpr (HR) L.stage_victims(slot, run, n0, pw);
+        #ifdef TW_STATS
+                if (run && ((pw >> 17) & 1u)) { STATL(K_KPOP); pkind = 2; }
+        #endif
                 STIME(tp0);
                 L.prefetch_all(run ? slot : 0xFFFFFFFFu);
                 STIME(tl1);
@@ -3164,6 +3144,8 @@ tw_run_kernel(Dev c, int64_t t_end, uint64_t max_events, uint32_t budget) {
                 alive = alive && L.status == TW_REP_RUNNING;
                 STIME(tl2);
                 STADDL(K_CYC_TAIL, tl2 - tl1);
+                STADDL(K_CYC_VIT, pkind == 1 ? tl2 - tl0 : 0);
+                STADDL(K_CYC_KIT, pkind == 2 ? tl2 - tl0 : 0);
             }
             L.hash_flush();
             __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)

@@ -24,7 +24,11 @@ NAMES = ["pop", "superseded", "peek_pf", "peek_hbm", "put_hbm", "put_dead", "pf_
          "near_push", "run_push", "far_push", "insn", "cyc_pop", "cyc_interp", "cyc_step_and_flush",
          "cyc_select", "cyc_fetch", "cyc_qpop", "cyc_commit", "cyc_prefetch", "cyc_terminal", "cyc_store", "cyc_hash",
          "cyc_spawn", "cyc_enqueue", "spawn", "alloc_ld", "iter", "cyc_send", "cyc_deliver", "cyc_due", "cyc_pro",
-         "cyc_epi", "cyc_ip", "pass"]
+         "cyc_epi", "cyc_ip", "pass",
+         # the teardown's two kinds of pop -- a kill wake (its step opens with throwTo) and a victim (the popped
+         # thread died of its pending exception) -- with the cycles of their iterations, and the lane-iterations
+         # in which no lane of the wave had a thread to run
+         "kill_pop", "victim_pop", "cyc_kill_iter", "cyc_victim_iter", "norun_iter"]
 
 
 def read(eng, heavy=False):
@@ -113,6 +117,10 @@ def main():
         pops = max(d["pop"], 1)
         rec = {"phase": name, "events": st.events, "kernel_ms": round(ms, 3),
                "ev_per_s": st.events / max(ms, 1e-9) * 1e3,
+               "kill_pop_share": round(d["kill_pop"] / pops, 4), "victim_pop_share": round(d["victim_pop"] / pops, 4),
+               "cyc_per_kill_pop": round(d["cyc_kill_iter"] / max(d["kill_pop"], 1), 1),
+               "cyc_per_victim_pop": round(d["cyc_victim_iter"] / max(d["victim_pop"], 1), 1),
+               "norun_iter_share": round(d["norun_iter"] / max(d["iter"], 1), 4),
                "per_pop": {k: round(v / pops, 4) for k, v in d.items() if k not in ("pop", "bat_phase_cyc")}, "counters": d}
         print(json.dumps(rec), flush=True)
 
