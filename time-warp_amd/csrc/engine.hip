@@ -611,16 +611,6 @@ static int load_common(tw_shard* c, const tw_scenario_desc* s, bool lp, uint32_t
         ALLOC(d.heavy, c->heavy_ok ? 2 * R : 2);
         ALLOC(d.heavy_n, 2);
         if (lpb) ALLOC(d.bat_ctr, 2);
-        // tw_lp_due_batch's deferred marks: at most one per batched reply, and a
-        // window's replies fit its outbox
-        d.dmk = nullptr;
-        d.dmk_n = nullptr;
-        d.dmk_cap = 0;
-        if (lpb && c->heavy_ok) {
-            d.dmk_cap = d.out_cap;
-            ALLOC(d.dmk, (size_t)2 * d.dmk_cap);
-            ALLOC(d.dmk_n, 2);
-        }
         ALLOC(d.pend_min, 1);
         ALLOC(d.inbox_n, 2 * R);
         ALLOC(d.outbox, (size_t)d.out_cap * 2);
@@ -764,7 +754,6 @@ int sh_reset(tw_shard* c) {
         HIPCHK(hipMemsetAsync(d.hash_g, 0, 8ull * ((size_t)d.Ntot << d.rep_lg), st));
         HIPCHK(hipMemsetAsync(d.heavy_n, 0, 8, st));
         if (d.bat_ctr) HIPCHK(hipMemsetAsync(d.bat_ctr, 0, 16, st));
-        if (d.dmk_n) HIPCHK(hipMemsetAsync(d.dmk_n, 0, 8, st));
         if (d.inlist) HIPCHK(hipMemsetAsync(d.inlist, 0, 4ull * R, st));
         HIPCHK(hipMemsetAsync(d.pend_min, 0xFF, 8, st));
         HIPCHK(hipMemsetAsync(d.out_n, 0, 4, st));
@@ -1256,19 +1245,14 @@ int sh_lp_clear_xmax(tw_shard* c) {
 // the window is fresh): the heavy lanes' due runs (tw_lp_due), the work list
 // from the last window's marks (tw_lpb_compact / tw_lp_compact), then the
 // due runs' batchable prefixes (tw_lp_batch: its replies' marks are the next
-// window's, so after the list).  Where the batch runs, tw_lp_due_batch does
-// both in one pass over each heavy lane's records (round 6) and tw_lp_dmark
-// makes its marks after the list -- measured slower (C5 1,463 -> 1,708 ms per
-// step: one 89-KB workgroup per CU runs the batch's dry runs that the separate
-// tw_lp_batch runs three workgroups per CU wide), so only with
-// TW_LP_FUSED=1 (A/B).
+// window's, so after the list).  (Tried both in one pass over each heavy
+// lane's records: C5 1,463 -> 1,708 ms per step -- one 89-KB workgroup per CU
+// ran the batch's dry runs that the separate tw_lp_batch runs three workgroups
+// per CU wide)
 static int lp_window_start(tw_shard* c) {
-    static const bool fused = getenv("TW_LP_FUSED") && getenv("TW_LP_FUSED")[0] == '1';
     const bool bat = c->heavy_ok && c->d.lpc_bat;
-    const bool fuse = bat && fused && c->d.dmk;
     if (c->heavy_ok) {
-        if (fuse) hipLaunchKernelGGL(tw_lp_due_batch, dim3(TW_DUE_GRID), dim3(256), 0, c->stream, c->dwin());
-        else hipLaunchKernelGGL(tw_lp_due, dim3(TW_DUE_GRID), dim3(256), 0, c->stream, c->dwin());
+        hipLaunchKernelGGL(tw_lp_due, dim3(TW_DUE_GRID), dim3(256), 0, c->stream, c->dwin());
         HIPCHK(hipGetLastError());
     }
     if (c->d.rw) {  // per-replica windows: tiles of 64 replicas x one chunk of nodes, four per workgroup
@@ -1279,10 +1263,7 @@ static int lp_window_start(tw_shard* c) {
         hipLaunchKernelGGL(tw_lp_compact, dim3(compact_blocks(c->d.R)), dim3(256), 0, c->stream, c->dwin(), 0u, 0u);
     }
     HIPCHK(hipGetLastError());
-    if (fuse) {
-        hipLaunchKernelGGL(tw_lp_dmark, dim3(64), dim3(256), 0, c->stream, c->dwin());
-        HIPCHK(hipGetLastError());
-    } else if (bat) {
+    if (bat) {
         hipLaunchKernelGGL(tw_lp_batch, dim3(TW_DUE_GRID), dim3(TW_BAT_T), 0, c->stream, c->dwin());
         HIPCHK(hipGetLastError());
     }
@@ -1316,7 +1297,6 @@ int sh_lp_loop_begin(tw_shard* c) {
         HIPCHK(hipMemsetAsync(c->d.rw + RW_TICK * nrep, 0xFF, 8 * nrep * (RW_COUNT - RW_TICK), c->stream));
     }
     HIPCHK(hipMemsetAsync(c->d.lp_err, 0, 4, c->stream));
-    if (c->d.dmk_n) HIPCHK(hipMemsetAsync(c->d.dmk_n, 0, 8, c->stream));
     int rc = lp_window_start(c);
     if (rc) return rc;
     c->loop_ready = true;

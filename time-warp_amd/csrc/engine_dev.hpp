@@ -25,12 +25,14 @@
 #define TW_WG_LP 128
 #define TW_NEAR_LP 8      // an LP node queues few events: 8 on chip (4 workgroups per CU)
 #define TW_NEAR_COMPACT 8 // compact geometry: 8 on-chip entries per replica, no far runs
-// work-list buckets by pending delivery records (tw_lp_compact).  Measured
-// with 4 buckets: C4 1.45 vs 1.58 G events/s -- pending records do not predict
-// a node's events in the window (most arrive for later windows) -- so 1.
 // LP event kernel: a context of more lanes than this many workgroups hold
 // (16384 x 128 = 2M) launches this many, walking the work list grid-stride
 #define TW_LP_GRID 16384u
+// work-list buckets by pending delivery records (tw_lp_compact).  Measured
+// with 4 buckets: C4 1.45 vs 1.58 G events/s -- pending records do not predict
+// a node's events in the window (most arrive for later windows) -- so 1, and
+// tw_run_kernel serves one bucket only.  (Still a parameter because writing
+// tw_lp_compact for one list changed its register allocation.)
 #ifndef TW_LP_NB
 #define TW_LP_NB 1
 #endif
@@ -43,57 +45,16 @@
 #define TW_NARROW 64
 #endif
 #define TW_STEP_CAP (1u << 22)  // instructions per thread step (== oracle kStepCap)
-// store only the record quads an event changed (1), or the whole record of a
-// thread that stays queued (0, the default).  C3, quad-major records, r02:
-// 1 = 72 B written per event at 17.2 G events/s, 0 = 90 B at 17.8 G (the
-// register compares cost more issue than the bytes save: not HBM-bound)
-#ifndef TW_DIRTY_TAIL
-#define TW_DIRTY_TAIL 0
-#endif
 // store-tail sinks: 8 XCD groups x 4 quads x 256 lanes (record quads), then
 // one 16-B word per replica (the hash atomic's, kept apart: atomics to shared
 // addresses would serialise)
 #define TW_DUMMY_Q (8u * 256u)
 #define TW_DUMMY_REC (4u * TW_DUMMY_Q)
-// cold words (CW_*) in registers (1) or in the LDS cold-word array (0, the
-// default): in registers the dense kernel needs 68 AGPRs of spill space and
-// ran C3 at 16.5 vs 17.9 G events/s (r02)
-#ifndef TW_CW_REGS
-#define TW_CW_REGS 0
-#endif
 #define TW_TAIL_VMEM 9          // vector-memory ops of every iteration after the record prefetch
-#define TW_REAP_VMEM 1          // ... of a reap iteration (no lane of the wave runs a thread): the hash atomic alone
-// reap iterations (the run geometries but the sparse one): 0 builds the A/B baseline
-#ifndef TW_REAP
-#define TW_REAP 1
-#endif
+#define TW_REAP_VMEM 1          // ... of a reap iteration (no lane of the wave runs a thread): the hash atomic alone (DESIGN §3j)
 
 // LP event kernel: waves per SIMD it is built for (2: <= 256 registers, which
 // spills; 1: the AGPRs too, no scratch)
-// LP lanes: the per-lane interpreter pass (PL: a hot pass serves lanes at
-// different pcs) -- 0 for the A/B of the opcode-uniform pass
-#ifndef TW_LP_PL
-#define TW_LP_PL 0
-#endif
-// the record prefetch as the compiler's LDS-DMA builtin (1) or inline asm (0)
-#ifndef TW_DMA_BUILTIN
-#define TW_DMA_BUILTIN 0
-#endif
-#ifndef TW_LP_FOLDJ
-#define TW_LP_FOLDJ 1  // the LP kernels fold a jump into the pass before it (Lane::FOLDJ; 0: the A/B baseline)
-#endif
-// the run geometries' lock-step fast path (Lane::fast_run): measured slower
-// (C3 138.8 -> 144.3 ms per step), so off -- 1 builds it for A/B
-#ifndef TW_FAST
-#define TW_FAST 0
-#endif
-#ifndef TW_FAST_COMPACT
-#define TW_FAST_COMPACT 0  // ... in the compact geometry (C2)
-#endif
-#define TW_FAST_MAX 32u  // instructions per fast_run entry
-#ifndef TW_LP_FORKN
-#define TW_LP_FORKN 1  // the LP kernels run a counted cross-node fork loop in one pass (Lane::fork_loop; 0: A/B)
-#endif
 #ifndef TW_LP_WAVES
 #define TW_LP_WAVES 2
 #endif
@@ -143,7 +104,9 @@ using namespace tw;
 // the far-heap top, rarely-touched counters and the step's spawn/yield
 // staging.  Keeping them out of registers leaves the event loop a small
 // register footprint (one wave per SIMD issues every instruction itself; a
-// large live set turns into register shuffles on every path).
+// large live set turns into register shuffles on every path: tried them in
+// registers, the dense kernel then needs 68 AGPRs of spill space and ran C3 at
+// 16.5 vs 17.9 G events/s, r02).
 // The far runs' bookkeeping, as quads in LDS [RQ_*][TW_WG]: head and second
 // entry of each run in the queue-entry format {t lo, t hi, slot, seq}, the
 // tail {t lo, t hi, seq, length}, and the four head indices in one quad.
@@ -341,14 +304,13 @@ struct Lane {
     // the LP kernels fold only a jump (U_NJ): a main thread's counted fork loop
     // (`forM_ [1..N] fork`, examples/token-ring/Main.hs:65-68) takes two passes
     // per fork instead of three
-    static constexpr bool FOLDJ = HR || (LP && TW_LP_FOLDJ);
-    // the lock-step fast path (fast_run): the run geometries
-    static constexpr bool FAST = (HR && TW_FAST) || (!LP && !RUNS && TW_FAST_COMPACT);
-    // per-lane hot passes (lanes at different hot ops share a pass) pay off where
-    // lanes diverge -- logical processes and the few-replica sparse geometry; the
-    // dense replica geometry runs lock-step programs and keeps the cheaper
-    // opcode-uniform pass
-    static constexpr bool PL = (LP && TW_LP_PL) || WG < 64;
+    static constexpr bool FOLDJ = HR || LP;
+    // per-lane hot passes (lanes at different hot ops share a pass): the
+    // few-replica sparse geometry, whose lanes diverge.  The dense replica
+    // geometries run lock-step programs and keep the cheaper opcode-uniform
+    // pass, and so do LP lanes (tried per-lane there: the opcode-uniform pass
+    // won, C5 +5 %)
+    static constexpr bool PL = WG < 64;
     Dev c;  // by value: kernel arguments stay in SGPRs
     uint32_t r;       // replica
     // LDS (lane-offset pointers; element j at [j * WG])
@@ -357,16 +319,11 @@ struct Lane {
     int64_t LAS* rf;      // the running thread's registers r0..r3 during its step
     uint4 LAS* pfs;       // prefetch staging: quad q of the next pop's record at [q * WG]
     uint32_t pfs_wave;    // LDS byte address of this wave's staging (quad 0), wave-uniform
-    uint32_t LAS* cw;     // cold words [CW_*] in LDS (TW_CW_REGS=0)
+    uint32_t LAS* cw;     // cold words [CW_*] in LDS
     // a spawning instruction's child registers (4 x int64) as two lane-contiguous
     // quads [2][WG]: one 16-B LDS access per pair, and at a pop whose step opens
     // with throwTo the LDS-DMA target of the victims' header quads (stage_victims)
     uint4 LAS* qq;
-    // cold words in registers (replica kernels): every index is a constant, so no
-    // LDS round trip; the allocator parks them in AGPRs when tight.  The LP
-    // kernel runs two waves per SIMD (no AGPR room) and keeps them in LDS.
-    static constexpr bool CWR = TW_CW_REGS && !LP;
-    uint32_t cwr[CW_COUNT];
     uint4 LAS* rq;        // far runs' bookkeeping quads [RQ_*]
     const uint2 LAS* P;   // program image
     const uint32_t LAS* PU;  // its uop flags
@@ -382,7 +339,8 @@ struct Lane {
     uint32_t far_n;
     bool far_dirty;
     // the running thread's frames / pending-exception quad changed this step
-    // (the store tail then writes it; otherwise only the quads that changed)
+    // (unread since the store tail writes whole records; kept because taking it
+    // out changes the run kernels' code)
     bool q1d;
     int fsrc;  // -1 none, 0..TW_RUNS-1 run, TW_RUNS heap
     int64_t fmt;
@@ -432,14 +390,8 @@ struct Lane {
     __device__ __forceinline__ uint32_t dg(int w) const { return cw[(cw_count<LP>() + w) * WG]; }
     __device__ __forceinline__ void ds(int w, uint32_t v) { cw[(cw_count<LP>() + w) * WG] = v; }
     // cold words
-    __device__ __forceinline__ uint32_t cg(int w) const {
-        if constexpr (CWR) return cwr[w];
-        else return cw[w * WG];
-    }
-    __device__ __forceinline__ void cs(int w, uint32_t v) {
-        if constexpr (CWR) cwr[w] = v;
-        else cw[w * WG] = v;
-    }
+    __device__ __forceinline__ uint32_t cg(int w) const { return cw[w * WG]; }
+    __device__ __forceinline__ void cs(int w, uint32_t v) { cw[w * WG] = v; }
     __device__ __forceinline__ int64_t cg64(int wl, int wh) const {
         return (int64_t)(((uint64_t)cg(wh) << 32) | cg(wl));
     }
@@ -1042,11 +994,13 @@ struct Lane {
     // The iteration's stores: the same NUMBER of vector-memory instructions on
     // every path (so the next pop's counted vmcnt wait proves the prefetch
     // landed without waiting for them), but each lane writes to HBM only what
-    // changed: the header quad of its thread (pc, flags, wake seq), the frames /
-    // exception quad when q1d, each register quad when its registers differ
-    // from the record's, and a forked child's whole record.  A quad with
-    // nothing to write goes to the lane's dummy sink (a few L2-resident lines
-    // per lane), so no store sits behind a branch or an exec mask.
+    // it must: the header quad of its thread (pc, flags, wake seq) when that
+    // changed, the whole record of a thread that stays queued, and a forked
+    // child's whole record.  A quad with nothing to write goes to the lane's
+    // dummy sink (a few L2-resident lines per lane), so no store sits behind a
+    // branch or an exec mask.  (Tried writing only the quads an event changed:
+    // 72 vs 90 B per event but 17.2 vs 17.8 G events/s on C3 -- the register
+    // compares cost more issue than the bytes save; DESIGN "Not HBM-bound".)
     __device__ __forceinline__ void store_tail(uint32_t slot, Th& th, bool full, bool hdr, uint32_t cslot,
                                                const Th& ch) {
         // the record sinks are shared by the workgroups of one XCD (blocks are
@@ -1056,13 +1010,7 @@ struct Lane {
         const size_t R5 = TW_DUMMY_Q;
         const int64_t n0 = rg(th, 0), n1 = rg(th, 1), n2 = rg(th, 2), n3 = rg(th, 3);
         const bool w0q = full || hdr;
-#if TW_DIRTY_TAIL
-        const bool w1q = full && q1d;
-        const bool w2q = full && (n0 != th.r0 || n1 != th.r1);
-        const bool w3q = full && (n2 != th.r2 || n3 != th.r3);
-#else
         const bool w1q = full, w2q = full, w3q = full;
-#endif
         th.r0 = n0; th.r1 = n1; th.r2 = n2; th.r3 = n3;
         uint4 GAS* pr = hrec(slot);
         *(w0q ? pr : dm) = make_uint4(th.w0, th.w1, th.w2, th.w3);
@@ -1100,17 +1048,6 @@ struct Lane {
         const bool valid = s != 0xFFFFFFFFu && s != cur && s < c.S;
         STAT(K_PF_ISSUE);
         const uint4 GAS* p = hrec(valid ? s : 0u);
-#if TW_DMA_BUILTIN
-        // the compiler's own LDS-DMA instruction: its vector-memory count is
-        // modelled (inline asm is opaque to the wait-count pass, which then
-        // guarded the address registers with vmcnt waits where they were reused)
-        const uint32_t pw = (uint32_t)__builtin_amdgcn_readfirstlane((int)pfs_wave);
-        uint4 LAS* d0 = (uint4 LAS*)(size_t)pw;
-        __builtin_amdgcn_global_load_lds((const void GAS*)p, (void LAS*)d0, 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((const void GAS*)(p + c.RQ), (void LAS*)(d0 + WG), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((const void GAS*)(p + 2 * c.RQ), (void LAS*)(d0 + 2 * WG), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((const void GAS*)(p + 3 * c.RQ), (void LAS*)(d0 + 3 * WG), 16, 0, 0);
-#else
         // (readfirstlane: the m0 operand is an SGPR whatever register the value was kept in)
         const uint32_t pw = (uint32_t)__builtin_amdgcn_readfirstlane((int)pfs_wave);
         // the instruction offset of global_load_lds also offsets the LDS
@@ -1123,7 +1060,6 @@ struct Lane {
                      "s"(pw + 2 * WG * 16) : "memory", "m0");
         asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off ; tw:pf" ::"v"(p + 3 * c.RQ),
                      "s"(pw + 3 * WG * 16) : "memory", "m0");
-#endif
         pf_slot = valid ? s : 0xFFFFFFFFu;
     }
     // The popped thread's record: the prefetched copy, or (rarely) a fresh load
@@ -1531,8 +1467,7 @@ struct Lane {
     }
     // predicated cold-word store: idle lanes write a dummy word (no branch)
     __device__ __forceinline__ void csp(bool p, int w, uint32_t v) {
-        if constexpr (CWR) cwr[w] = p ? v : cwr[w];
-        else cw[(p ? w : CW_DUMMY) * WG] = v;  // idle lanes write a dummy word (no branch)
+        cw[(p ? w : CW_DUMMY) * WG] = v;
     }
 
     enum { T_NONE, T_YIELD, T_SPAWN, T_EXIT, T_STOP, T_DIED };
@@ -1689,7 +1624,7 @@ struct Lane {
                             }
                             tc = go ? (uint32_t)T_YIELD : tc;
                             yt = go ? now + 1 : yt;
-                            if (TW_LP_FORKN && __builtin_amdgcn_ballot_w64(go && (lfl & U_FL)))
+                            if (__builtin_amdgcn_ballot_w64(go && (lfl & U_FL)))
                                 if (go && (lfl & U_FL)) fork_loop(th, n, pc, (uint32_t)imm, a, b, tgt, tc, yt);
                         }
                     }
@@ -2181,135 +2116,9 @@ struct Lane {
         tgt = pc + 1u;
     }
 
-    // Lock-step fast path (round 6, the run geometries: TW_FAST).  When every
-    // running lane of the wave is at the same pc -- the replicas of one
-    // scenario step through the same code, e.g. C3's start-up: main's `forM_
-    // fork launchNode`, launchNode's forks, the worker's `catch ; sleepForever`,
-    // the server's `listen ; sleepForever` (examples/token-ring/Main.hs:
-    // 65-68,104-135) -- the instruction is one scalar word: it is read once
-    // (an LDS broadcast) and decoded in SGPRs, and its body is the op's own
-    // few vector instructions.  Consecutive instructions run in one loop, and
-    // the step's terminal (a wait's yield, END, FORK) leaves it, with no
-    // general pass -- whose per-lane decode, opcode-uniform lane match, class
-    // branches, fold checks and epilogue cost ~2.4k cycles per instruction
-    // (tools/stats_probe.py).  The semantics are the pass's,
-    // instruction for instruction: the same counts n (the 2^22 cap), register
-    // writes, node variable / binding / frame stores, hash terms and terminal
-    // staging.  Anything else -- a rare op, a fused pair, a jump the lanes
-    // take differently, an instruction that would fail (a bad node, frames
-    // over the cap, an out-of-range target, the step cap) -- leaves the lanes
-    // at its pc for the general pass, which executes it exactly as before.
-    __device__ __forceinline__ void fast_run(Th& th, uint32_t slot, St& s) {
-        const uint64_t rm = __builtin_amdgcn_ballot_w64(s.running);
-        if (!rm) return;
-        uint32_t fp = __builtin_amdgcn_readlane(s.pc, (uint32_t)__builtin_ctzll(rm));
-        if (__builtin_amdgcn_ballot_w64(s.running && s.pc != fp)) return;  // lanes at different pcs
-        const bool run = s.running;
-        for (uint32_t k = 0; k < TW_FAST_MAX; ++k) {
-            // (the image's last instruction goes to the general pass: running off
-            // the end is its error, counted as it counts it)
-            if (fp + 1u >= c.n_insns || __builtin_amdgcn_ballot_w64(run && s.n >= TW_STEP_CAP)) break;
-            const uint2 in = P[fp];
-            const uint32_t w = __builtin_amdgcn_readfirstlane(in.x);
-            const int32_t imm = (int32_t)__builtin_amdgcn_readfirstlane(in.y);
-            const uint32_t op = w & 0xFFu, a = (w >> 8) & 3u, b = w >> 16;
-            uint32_t nx = fp + 1u;      // the next pc (uniform)
-            uint32_t fin = T_NONE;      // a terminal: every running lane leaves the step
-            if (op == TW_OP_FORK) {     // r[a] <- ref(child) at the terminal (TimedT.hs:326-342)
-                const uint32_t node = b == 0xFFFFu ? th.w1 : (uint32_t)rg(th, b & 3u);
-                if (__builtin_amdgcn_ballot_w64(run && node >= c.N)) break;
-                csp(run, CW_CSP, csp_word((uint32_t)imm, a, 2u));  // the child's registers are the parent's
-                csp(run, CW_CNODE, node);
-                fin = T_SPAWN;
-            } else if (op == TW_OP_WAIT_REL || op == TW_OP_WAIT_ABS || op == TW_OP_WAIT_REG) {
-                int64_t wt;
-                if (op == TW_OP_WAIT_REG) {
-                    const int64_t ra = rg(th, a);
-                    wt = now + (ra > 0 ? ra : 0);
-                } else {
-                    const int64_t kt = K[imm];
-                    wt = op == TW_OP_WAIT_REL ? now + kt : (kt > now ? kt : now);
-                }
-                s.yt = run ? wt : s.yt;
-                fin = T_YIELD;
-            } else if (op == TW_OP_END) {
-                fin = T_EXIT;
-            } else if (op == TW_OP_JMP) {
-                if ((uint32_t)imm >= c.n_insns) break;
-                nx = (uint32_t)imm;
-            } else if (op >= TW_OP_JEQ && op <= TW_OP_JNEI) {
-                if ((uint32_t)imm >= c.n_insns) break;
-                const int64_t ra = rg(th, a), rb = rg(th, b & 3u), bi = (int64_t)(int16_t)b;
-                const bool tk = op == TW_OP_JEQ ? ra == rb : op == TW_OP_JNE ? ra != rb : op == TW_OP_JLT ? ra < rb
-                              : op == TW_OP_JLE ? ra <= rb : op == TW_OP_JEQI ? ra == bi : ra != bi;
-                const uint64_t tm = __builtin_amdgcn_ballot_w64(run && tk);
-                if (tm != 0 && tm != rm) break;  // the lanes part ways: the general pass
-                nx = tm ? (uint32_t)imm : nx;
-            } else if (op == TW_OP_SETI || op == TW_OP_SETK || op == TW_OP_ADDI || op == TW_OP_MULI ||
-                       op == TW_OP_MOV || op == TW_OP_ADD || op == TW_OP_SUB || op == TW_OP_NOW ||
-                       op == TW_OP_NODE || op == TW_OP_MYTID) {
-                const bool two = op == TW_OP_MOV || op == TW_OP_ADD || op == TW_OP_SUB;
-                if (!two && op != TW_OP_MYTID && (b & TW_ALU_NSTORE)) break;  // a fused pair
-                const int64_t ra = rg(th, a);
-                const int64_t rb = two ? rg(th, b & 3u) : 0;
-                int64_t v;
-                if (op == TW_OP_SETI) v = imm;
-                else if (op == TW_OP_SETK) v = K[imm];
-                else if (op == TW_OP_ADDI) v = ra + (int64_t)imm;
-                else if (op == TW_OP_MULI) v = ra * (int64_t)imm;
-                else if (op == TW_OP_MOV) v = rb;
-                else if (op == TW_OP_ADD) v = ra + rb;
-                else if (op == TW_OP_SUB) v = ra - rb;
-                else if (op == TW_OP_NOW) v = now;
-                else if (op == TW_OP_NODE) v = (int64_t)th.w1;
-                else v = (int64_t)(((uint64_t)th.w2 << 32) | slot);
-                rs(th, a, run ? v : ra);
-            } else if (op == TW_OP_NLOAD) {
-                const int64_t x = gp(c.nvars)[nix(run ? th.w1 : 0u, b & 3u)];
-                tw_vm_drain();
-                if (run) rs(th, a, x);
-            } else if (op == TW_OP_NSTORE) {
-                const int64_t ra = rg(th, a);
-                if (run) gp(c.nvars)[nix(th.w1, b & 3u)] = ra;
-            } else if (op == TW_OP_TRACE) {
-                if (c.trace_cap || (b & TW_TRACE_PAIR)) break;
-                const int64_t ra = rg(th, a);
-                hacc += run ? term(now, TW_KIND_TRACE | ((uint32_t)imm & 0xFFFFu), ra) : 0ull;
-            } else if (op == TW_OP_CATCH) {
-                const uint32_t nf = th_nfr(th);
-                if (__builtin_amdgcn_ballot_w64(run && nf >= c.max_frames)) break;
-                const uint32_t fv = (b << 16) | ((uint32_t)imm & 0xFFFFu);
-                th.f0 = (run && nf == 0) ? fv : th.f0;
-                th.f1 = (run && nf == 1) ? fv : th.f1;
-                q1d = q1d || (run && nf < 2);
-                if (run && nf >= 2) *fxp(slot, nf) = fv;  // deeper frames: the overflow area
-                th.w0 = run ? (th.w0 & ~(15u << 16)) | ((nf + 1) << 16) : th.w0;
-            } else if (op == TW_OP_LISTEN) {
-                if ((uint32_t)imm >= c.n_sets) break;
-                if (run) {
-                    gp(c.bind)[bix(th.w1)] = (uint32_t)imm + 1;
-                    gp(c.bind_own)[bix(th.w1)] = b ? th.w2 : 0xFFFFFFFFu;
-                }
-                th.w0 = (run && b) ? th.w0 | (F_OWNS << FL_SHIFT) : th.w0;
-            } else if (op == TW_OP_UNLISTEN) {
-                if (run) {
-                    gp(c.bind)[bix(th.w1)] = 0;
-                    gp(c.bind_own)[bix(th.w1)] = 0xFFFFFFFFu;
-                }
-            } else if (op != TW_OP_NOP) {
-                break;  // a rare op: the general pass
-            }
-            STAT(K_INSN);
-            s.n += run ? 1u : 0u;
-            fp = nx;
-            if (fin != T_NONE) {
-                s.fin = run ? fin : s.fin;
-                s.running = false;
-                break;
-            }
-        }
-        s.pc = run ? fp : s.pc;
-    }
+    // (Tried a lock-step fast path for waves whose running lanes share one pc,
+    // decoding the instruction once in SGPRs: C3 138.8 -> 144.3 ms per step, so
+    // removed)
 
     // A fork whose child is the very next pop runs the child in place, in this
     // iteration (replica kernels).  TimedT's fork queues the child at now and
@@ -2442,10 +2251,6 @@ struct Lane {
                     if (more) continue;
                 }
                 break;
-            }
-            if constexpr (FAST) {
-                fast_run(th, slot, s);
-                if (!__builtin_amdgcn_ballot_w64(s.running)) continue;
             }
             const uint32_t first = (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(s.running));
             // every lane fetches its own instruction; the pass runs the first running
@@ -2661,10 +2466,7 @@ __host__ __device__ constexpr size_t fixed_lds_bytes() {
 // per SIMD (<= 256 registers, half the LDS of a dense lane), so 1M-replica
 // batches keep two workgroups per CU
 // LP lanes' prologue: the near spill's entries and the far heap's top loaded
-// together (round 6: C5 1,366 -> 1,341 ms, C4 flat; TW_LP_PRO=0 for the A/B)
-#ifndef TW_LP_PRO
-#define TW_LP_PRO 1
-#endif
+// together (round 6: C5 1,366 -> 1,341 ms, C4 flat)
 template <bool LP, int WG, int NC, int TPW = 64, bool RUNS = true, bool GS = false, bool PRW = false, bool IP = false>
 __global__ void __launch_bounds__(WG * 64 / TPW)
     __attribute__((amdgpu_waves_per_eu(LP ? TW_LP_WAVES : !RUNS ? 2 : (WG * 64 / TPW + 255) / 256,
@@ -2717,11 +2519,11 @@ tw_run_kernel(Dev c, int64_t t_end, uint64_t max_events, uint32_t budget) {
             s_p[i] = in;
             uint32_t u = uop_insn(in.x);
             auto is_end = [&](uint32_t j) { return j < c.n_insns && (gp(c.insns)[j].x & 0xFFu) == TW_OP_END; };
-            if (LP && TW_LP_FOLDJ && i < c.n_insns) {  // (Lane::FOLDJ: a jump only)
+            if (LP && i < c.n_insns) {  // (Lane::FOLDJ: a jump only)
                 const uint32_t nop = i + 1u < c.n_insns ? gp(c.insns)[i + 1u].x & 0xFFu : TW_OP_NOP;
                 u |= U_JM(uop_of(nop)) != JM_NONE ? U_NJ : 0u;
             }
-            if (LP && TW_LP_FORKN && c.lpb && i + 2u < c.n_insns && (in.x & 0xFFu) == TW_OP_FORK &&
+            if (LP && c.lpb && i + 2u < c.n_insns && (in.x & 0xFFu) == TW_OP_FORK &&
                 (in.x >> 16) != 0xFFFFu) {  // (Lane::fork_loop)
                 const uint32_t w1 = gp(c.insns)[i + 1u].x;
                 const uint2 j2 = gp(c.insns)[i + 2u];
@@ -2845,7 +2647,7 @@ tw_run_kernel(Dev c, int64_t t_end, uint64_t max_events, uint32_t budget) {
             L.ev_room = ev_room;
             L.d_ev = 0;
             L.d_th = 0;
-            if constexpr (LP && TW_LP_PRO) {
+            if constexpr (LP) {
                 // (loaded whether or not the heap holds anything, so the load
                 // goes out with the scalar block's instead of after it; CW_FT*
                 // are read only while far_n > 0)
@@ -2900,7 +2702,7 @@ tw_run_kernel(Dev c, int64_t t_end, uint64_t max_events, uint32_t budget) {
             // ahead for a 32-bit key (or an oversized spill) takes the pushing path.
             L.nbase = L.now;
             L.near_init();
-            if constexpr (LP && TW_LP_PRO) {
+            if constexpr (LP) {
                 // (an LP lane reloads its spill every window: its entries are
                 // loaded together, one round trip, instead of one after another)
                 uint4 se[NC];
@@ -3069,7 +2871,7 @@ tw_run_kernel(Dev c, int64_t t_end, uint64_t max_events, uint32_t budget) {
             // with its own wait count), so each counted wait is a literal whose
             // count holds on every path that reaches it (tools/waitcnt_audit.py).
             // Every other kernel's loop body is the one it always had.
-            constexpr bool REAP = HR && WG >= 64 && TW_REAP;
+            constexpr bool REAP = HR && WG >= 64;
         #ifdef TW_STATS
             uint64_t tl0 = 0;
             uint32_t pkind = 0;  // this iteration's pop: 1 a victim (died of its pending exception), 2 a kill wake
@@ -3919,7 +3721,7 @@ struct DueX {
 // Lane::emit for a record of the batch (the thread's own append: no wave
 // aggregation); returns 1 for a record written straight into a light inbox
 __device__ __forceinline__ uint32_t due_emit(const Dev& c, uint32_t wid, int64_t ta, int64_t payload, uint32_t link,
-                                             uint32_t kind, uint32_t src, uint32_t dst, uint4 dh, bool defer = false) {
+                                             uint32_t kind, uint32_t src, uint32_t dst, uint4 dh) {
     const uint4 q0 = make_uint4((uint32_t)ta, (uint32_t)((uint64_t)ta >> 32), (uint32_t)payload,
                                 (uint32_t)((uint64_t)payload >> 32));
     const uint4 q1 = make_uint4(link, kind, src, dst);
@@ -3936,14 +3738,7 @@ __device__ __forceinline__ uint32_t due_emit(const Dev& c, uint32_t wid, int64_t
         uint4 GAS* q = gp(c.inbox) + ((size_t)par * c.ib_total + base + (size_t)k * ib_stride(c, false)) * 2;
         q[0] = q0;
         q[1] = q1;
-        if (defer) {  // (tw_lp_due_batch runs before the window's list is built: tw_lp_dmark marks it after)
-            const uint32_t j = __hip_atomic_fetch_add(gp(c.dmk_n) + (wid & 1u), 1u, __ATOMIC_RELAXED,
-                                                      __HIP_MEMORY_SCOPE_AGENT);
-            if (j < c.dmk_cap) gp(c.dmk)[(size_t)(wid & 1u) * c.dmk_cap + j] = lp;
-            else __hip_atomic_fetch_or(gp(c.lp_err), 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            lp_mark(c, lp, wid);
-        }
+        lp_mark(c, lp, wid);
         return 1u;
     }
     const uint32_t i = __hip_atomic_fetch_add(gp(c.out_n), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -4104,12 +3899,11 @@ __device__ DueX due_exec(const Dev& c, const BProg& bp, uint32_t r, uint32_t set
 // The effects of a batched record beyond its lane (due_exec's data): the
 // sending node's term, the send's record; returns 1 for a record written
 // straight into a light inbox
-__device__ __forceinline__ uint32_t due_effects(const Dev& c, uint32_t wid, uint32_t node, const DueX& x,
-                                                bool defer = false) {
+__device__ __forceinline__ uint32_t due_effects(const Dev& c, uint32_t wid, uint32_t node, const DueX& x) {
     if (x.hs_lane != 0xFFFFFFFFu)
         __hip_atomic_fetch_add((unsigned long long GAS*)(gp(c.hash_g) + x.hs_lane), (unsigned long long)x.hs,
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return x.yld ? due_emit(c, wid, x.ta, x.pay, x.lk, x.k2, node, x.dst, x.dh, defer) : 0u;
+    return x.yld ? due_emit(c, wid, x.ta, x.pay, x.lk, x.k2, node, x.dst, x.dh) : 0u;
 }
 
 __global__ void __launch_bounds__(256) tw_lp_due(Dev c) {
@@ -4310,11 +4104,13 @@ __global__ void __launch_bounds__(256) tw_lp_due(Dev c) {
 // share a CU at the kernel's two waves per SIMD -- a heavy lane's pass is a
 // chain of round trips and barriers, and twice the lanes in flight halve the
 // rounds (four waves per workgroup: two per CU)
-#ifndef TW_BAT_T
 #define TW_BAT_T 128u
-#endif
 #define TW_BAT_RPT (TW_BATCH_CAP / TW_BAT_T)  // records per thread in the prefix scan
 static_assert(TW_BAT_T % 64 == 0 && TW_BAT_T <= 256 && TW_BATCH_CAP % TW_BAT_T == 0, "batch workgroup shape");
+// the lane's scalar block is loaded by threads 0..SC_COUNT-1, and its near
+// spill, far-heap top and spawn count by threads 64..65+TW_NEAR_LP (wave 1):
+// a narrower workgroup would leave sS / sNear / bFarT / bSpn unwritten
+static_assert(SC_COUNT <= TW_BAT_T && 66u + TW_NEAR_LP <= TW_BAT_T, "tw_lp_batch's loader threads exist");
 __global__ void __launch_bounds__(TW_BAT_T) tw_lp_batch(Dev c) {
     const int64_t GAS* w = gp(c.win);
     const int64_t fl = w[WN_FLAGS];
@@ -4525,349 +4321,6 @@ __global__ void __launch_bounds__(TW_BAT_T) tw_lp_batch(Dev c) {
                                    __HIP_MEMORY_SCOPE_AGENT);
 #endif
 #undef BT
-}
-
-// ---------------------------------------------------------------------------
-// tw_lp_due + tw_lp_batch in one pass over a heavy lane's records (round 6,
-// DESIGN §3i; TW_LP_FUSED=1 -- measured slower than the two kernels, so not
-// the default).  A heavy lane's inbox is staged in LDS once: the records
-// due in the window are sorted into the due run as tw_lp_due sorts them
-// (timestamp bins, then rec_less inside a bin), their reply links looked up
-// once, and the batch's dry run, prefix and effects (tw_lp_batch) run on the
-// sorted records in LDS -- no second read of the due run, no second launch,
-// and only the records the batch leaves (positions [K, nd)) are written back
-// as the due run.  The one ordering the two kernels kept: the window's work
-// list (tw_lpb_compact) is built from the marks of the window before, and a
-// batched reply delivered straight into a light lane's inbox marks that lane
-// for the window after -- made now, before the list is built, the mark would
-// hide the one the list reads.  So those lanes are recorded (Dev::dmk, by
-// window parity) and marked by tw_lp_dmark right after the list is built.
-// Everything else is tw_lp_due's and tw_lp_batch's code path for path: the
-// reserved seqs of the due run, the records left for later windows and their
-// minimum, the heavy list of the next window, the batch's eligibility and
-// totals.
-__global__ void __launch_bounds__(256) tw_lp_due_batch(Dev c) {
-    const int64_t GAS* w = gp(c.win);
-    const int64_t fl = w[WN_FLAGS];
-    if (!(fl & WN_FRESH) || (fl & WN_DONE)) return;
-    const uint32_t wid = (uint32_t)w[WN_WID];
-    const int64_t T0 = w[WN_T], L = w[WN_L];
-    const bool radix = L <= TW_DUE_BINS;
-    const uint32_t nb = radix ? (uint32_t)L : 0u;
-    const uint32_t lst = wid & 1u;
-    uint32_t nh = gp(c.heavy_n)[lst];
-    nh = nh < c.R ? nh : c.R;  // (an over-full list has set lp_err)
-    if (blockIdx.x >= nh) return;
-    // the batch needs the program tables in LDS (a program over the caps is
-    // only sorted, as tw_lp_due alone would)
-    const bool tables = c.lpc_bat && c.n_insns <= TW_BATCH_INSNS && c.n_consts <= TW_BATCH_CONSTS &&
-                        c.n_sets * c.n_kinds <= TW_BATCH_LPC;
-    __shared__ uint4 ea[TW_HEAVY_CAP], eb[TW_HEAVY_CAP];
-    __shared__ uint16_t dix[TW_HEAVY_CAP];  // entry index of the i-th due record (arrival order); then batch flags
-    __shared__ uint16_t srt[TW_HEAVY_CAP];  // ... of the i-th due record in due-run order
-    __shared__ uint32_t bins[TW_DUE_BINS];
-    __shared__ uint32_t wsum[4];
-    __shared__ unsigned long long smin;
-    __shared__ uint2 sP[TW_BATCH_INSNS];
-    __shared__ int64_t sK[TW_BATCH_CONSTS];
-    __shared__ uint32_t sL[TW_BATCH_LPC];
-    __shared__ uint8_t sB[TW_BATCH_LPC];
-    __shared__ int64_t wmx[4], sNear[8];
-    __shared__ uint64_t sS[SC_COUNT];
-    __shared__ uint32_t bSet, bK0, bK, bDirect, bNd;
-    __shared__ int64_t bTo;
-    __shared__ unsigned long long bH, bsum[6];
-    __shared__ long long bFin, bLast;
-    static_assert(TW_HEAVY_CAP == 256 * 8, "eight entries per thread");
-    static_assert(TW_DUE_BINS == 256 * 8, "eight bins per thread");
-    static_assert(TW_BATCH_CAP == 256 * 4, "four prefix positions per thread");
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    if (tables) {
-        for (uint32_t i = tid; i < c.n_insns; i += 256) sP[i] = gp(c.insns)[i];
-        for (uint32_t i = tid; i < c.n_consts; i += 256) sK[i] = gp(c.consts)[i];
-        for (uint32_t i = tid; i < c.n_sets * c.n_kinds; i += 256) {
-            sL[i] = gp(c.lpc)[i];
-            sB[i] = gp(c.lpc_bat)[i];
-        }
-    }
-    const BProg bp{(const uint2 LAS*)sP, (const int64_t LAS*)sK, (const uint32_t LAS*)sL, (const uint8_t LAS*)sB};
-    uint8_t* bfl = (uint8_t*)dix;  // (batch flags per due position, once dix is consumed)
-    const size_t st = ib_stride(c, true);  // (heavy lanes only)
-    for (uint32_t hi = blockIdx.x; hi < nh; hi += gridDim.x) {
-        const uint32_t r = gp(c.heavy)[(size_t)lst * c.R + hi];
-        const int64_t T = c.rw ? *rw_at(c, RW_T, r) : T0;
-        if (T == INT64_MAX) continue;  // (a finished replica has no records; uniform)
-        const int64_t tend = T + L - 1;
-        uint64_t* sc = gp(c.scal) + (size_t)r * SC_LP_STRIDE;  // (LP: the lane's block)
-        __syncthreads();  // (the previous lane's readers of the shared words are done)
-        uint32_t n = gp(c.inbox_n)[r];
-        const uint32_t cap = ib_cap(c, r);
-        n = n < cap ? n : cap;
-        const size_t ib = ib_base(c, r);
-        for (uint32_t k = tid; k < n; k += 256) {
-            const uint4 GAS* q = gp(c.inbox) + (ib + (size_t)k * st) * 2;
-            ea[k] = q[0];
-            eb[k] = q[1];
-        }
-        if (tid < SC_COUNT) sS[tid] = sc[tid];
-        if (tid == 0) {
-            smin = ~0ull;
-            const uint32_t own = gp(c.bind_own)[r], rel = gp(c.bind_rel)[r];
-            bSet = own == rel ? 0u : gp(c.bind)[r];
-            bK = 0;
-            bDirect = 0;
-            bH = 0;
-            bFin = INT64_MIN;
-            bLast = INT64_MIN;
-            for (int j = 0; j < 6; ++j) bsum[j] = 0;
-        }
-        if (tid < 8u) {  // the lane's next queued event: its near spill and far heap top
-            int64_t x = INT64_MAX;
-            if (tid < (uint32_t)sc[SC_NEAR_N]) x = ent_t(gp(c.near_spill)[(size_t)tid * c.R + r]);
-            if (tid == 0 && sc[SC_FAR_N]) {
-                const int64_t f = ent_t(gp(c.far)[r]);
-                x = f < x ? f : x;
-            }
-            sNear[tid] = x;
-        }
-        for (uint32_t i = tid; i < nb; i += 256) bins[i] = 0;
-        __syncthreads();
-        // ---- tw_lp_due: due flags, a scan, the due records' arrival indices
-        // and timestamp bins, the rest compacted back into the inbox
-        uint32_t my = 0;
-        for (uint32_t j = 0; j < 8; ++j) {
-            const uint32_t k = tid * 8 + j;
-            my += (k < n && ent_t(ea[k]) <= tend) ? 1u : 0u;
-        }
-        uint32_t nd = 0;
-        uint32_t before = wg_excl_scan(my, wsum, &nd);
-        unsigned long long mn = ~0ull;
-        for (uint32_t j = 0; j < 8; ++j) {
-            const uint32_t k = tid * 8 + j;
-            if (k >= n) break;
-            const int64_t t = ent_t(ea[k]);
-            if (t <= tend) {
-                dix[before++] = (uint16_t)k;
-                if (radix) atomicAdd(&bins[t > T ? (uint32_t)(t - T) : 0u], 1u);
-            } else {
-                uint4 GAS* q = gp(c.inbox) + (ib + (size_t)(k - before) * st) * 2;
-                q[0] = ea[k];
-                q[1] = eb[k];
-                mn = (unsigned long long)t < mn ? (unsigned long long)t : mn;
-            }
-        }
-        if (mn != ~0ull) atomicMin(&smin, mn);
-        __syncthreads();
-        if (radix) {
-            uint32_t cnt8[8], sum = 0;
-            for (uint32_t j = 0; j < 8; ++j) {
-                const uint32_t bi = tid * 8 + j;
-                cnt8[j] = bi < nb ? bins[bi] : 0u;
-                sum += cnt8[j];
-            }
-            uint32_t tot = 0;
-            uint32_t off = wg_excl_scan(sum, wsum, &tot);
-            for (uint32_t j = 0; j < 8; ++j) {
-                const uint32_t bi = tid * 8 + j;
-                if (bi < nb) bins[bi] = off;
-                off += cnt8[j];
-            }
-            __syncthreads();
-            for (uint32_t i = tid; i < nd; i += 256) {
-                const uint32_t k = dix[i];
-                const int64_t t = ent_t(ea[k]);
-                const uint32_t pos = atomicAdd(&bins[t > T ? (uint32_t)(t - T) : 0u], 1u);
-                srt[pos] = (uint16_t)k;
-            }
-            __syncthreads();
-            for (uint32_t bi = tid; bi < nb; bi += 256) {
-                const uint32_t s0 = bi ? bins[bi - 1] : 0u, s1 = bins[bi];
-                for (uint32_t x = s0 + 1; x < s1; ++x) {
-                    const uint16_t k = srt[x];
-                    uint32_t y = x;
-                    while (y > s0 && rec_less(ea[k], eb[k], ea[srt[y - 1]], eb[srt[y - 1]])) {
-                        srt[y] = srt[y - 1];
-                        --y;
-                    }
-                    srt[y] = k;
-                }
-            }
-        } else {
-            // long windows: rank of every due record among the due ones (ties by arrival)
-            for (uint32_t i = tid; i < nd; i += 256) {
-                const uint32_t k = dix[i];
-                const uint4 a = ea[k], b = eb[k];
-                uint32_t rank = 0;
-                for (uint32_t j = 0; j < nd; ++j) {
-                    const uint32_t m = dix[j];
-                    rank += (rec_less(ea[m], eb[m], a, b) || (j < i && !rec_less(a, b, ea[m], eb[m]))) ? 1u : 0u;
-                }
-                srt[rank] = (uint16_t)k;
-            }
-        }
-        __syncthreads();
-        // the due-run format of each due record: its reply link in place of the destination
-        for (uint32_t i = tid; i < nd; i += 256) {
-            const uint32_t k = srt[i];
-            eb[k] = due_rec_b(c, eb[k]);
-        }
-        // ---- tw_lp_batch's eligibility (the due run is fresh: seqs reserved below)
-        const uint64_t s0 = sS[SC_SEQ];
-        const bool ctr_ok = s0 + nd < 0xFFFFFFFFull;
-        if (tid == 0) {
-            const uint64_t sq = s0 + nd;  // (SC_SEQ after the due run's reservation)
-            const bool el = tables && nd && ctr_ok && c.trace_cap == 0 && c.tie_mode == TW_TIE_FIFO &&
-                            (sS[SC_FREE_N] > 0 || sS[SC_BUMP] < (uint64_t)c.S) &&
-                            sS[SC_STATUS] == TW_REP_RUNNING && sS[SC_PENDING_MAIN] == 0 &&
-                            !(c.lpb && gp(c.spawn_n)[r]) && sq + 3ull * nd < 0xFFFFFFFFull &&
-                            sS[SC_TIDC] + nd < 0xFFFFFFFFull;
-            bNd = el ? (nd < TW_BATCH_CAP ? nd : TW_BATCH_CAP) : 0u;
-            bK0 = bNd;
-            int64_t to = INT64_MAX;
-            for (int j = 0; j < 8; ++j) to = sNear[j] < to ? sNear[j] : to;
-            bTo = to;
-        }
-        __syncthreads();
-        const uint32_t nbt = bNd;  // (uniform)
-        uint32_t K = 0;
-        DueX x0{};
-        if (nbt) {
-            // dry run: batchable | yielded << 1 per record (due order)
-            for (uint32_t i = tid; i < nbt; i += 256) {
-                const uint32_t k = srt[i];
-                const DueX x = due_exec(c, bp, r, bSet, ea[k], eb[k]);
-                const bool ok = x.ok && x.last < bTo;
-                bfl[i] = (uint8_t)((ok ? 1u : 0u) | (x.yld ? 2u : 0u));
-                if (!ok) atomicMin(&bK0, i);
-                if (i == tid) x0 = x;
-            }
-            __syncthreads();
-            const uint32_t K0 = bK0;
-            // the latest resume before each position (an inclusive max scan)
-            int64_t cm = INT64_MIN;
-            for (uint32_t j = 0; j < 4; ++j) {
-                const uint32_t i = tid * 4 + j;
-                if (i < K0 && (bfl[i] & 2u)) {
-                    const int64_t y = ent_t(ea[srt[i]]) + 1;
-                    cm = y > cm ? y : cm;
-                }
-            }
-#pragma unroll
-            for (uint32_t d = 1; d < 64; d <<= 1) {
-                const int64_t o = __shfl_up(cm, d, 64);
-                if (lane >= d) cm = o > cm ? o : cm;
-            }
-            if (lane == 63) wmx[wv] = cm;
-            __syncthreads();
-            int64_t m = __shfl_up(cm, 1, 64);
-            if (lane == 0) m = INT64_MIN;
-            for (uint32_t k = 0; k < wv; ++k) m = wmx[k] > m ? wmx[k] : m;
-            // (the last thread also checks position TW_BATCH_CAP: the first record
-            // past the cap may close the prefix)
-            const uint32_t jn = tid == 255u ? 5u : 4u;
-            for (uint32_t j = 0; j < jn; ++j) {
-                const uint32_t i = tid * 4 + j;
-                if (i > K0) break;
-                // the prefix [0, i) is kept when its last resume precedes record
-                // i's wake (i = nbt: the first record past the cap, or none)
-                if (i == nbt && nd == nbt) { atomicMax(&bK, i); break; }
-                const int64_t ti = ent_t(ea[srt[i]]);
-                if (m < ti) atomicMax(&bK, i);
-                if (i < K0 && (bfl[i] & 2u)) m = ti + 1 > m ? ti + 1 : m;
-            }
-            __syncthreads();
-            K = bK;
-        }
-        // ---- the due run the chain pops: positions [K, nd) (the batch took [0, K))
-        for (uint32_t i = K + tid; i < nd; i += 256) {
-            const uint32_t k = srt[i];
-            uint4 GAS* q = gp(c.due) + (ib + (size_t)i * st) * 2;
-            q[0] = ea[k];
-            q[1] = eb[k];
-        }
-        // ---- the prefix for real: other nodes' hash terms, the sends' records
-        if (K) {
-            const uint32_t node = (c.lp0 + r) >> c.rep_lg;
-            uint64_t h = 0;
-            uint32_t sm[6] = {0, 0, 0, 0, 0, 0}, dir = 0;
-            int64_t fin = INT64_MIN, last = INT64_MIN;
-            for (uint32_t i = tid; i < K; i += 256) {
-                const uint32_t k = srt[i];
-                const DueX x = i == tid ? x0 : due_exec(c, bp, r, bSet, ea[k], eb[k]);
-                dir |= due_effects(c, wid, node, x, true);
-                h += x.h;
-                sm[0] += x.dl; sm[1] += x.ud; sm[2] += x.dr; sm[3] += x.ev; sm[4] += x.th; sm[5] += x.sq;
-                fin = x.fin > fin ? x.fin : fin;
-                last = x.last > last ? x.last : last;
-            }
-            if (h) atomicAdd(&bH, (unsigned long long)h);
-            for (int j = 0; j < 6; ++j)
-                if (sm[j]) atomicAdd(&bsum[j], (unsigned long long)sm[j]);
-            if (dir) bDirect = 1;
-            if (fin != INT64_MIN) atomicMax(&bFin, (long long)fin);
-            if (last != INT64_MIN) atomicMax(&bLast, (long long)last);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            // tw_lp_due's bookkeeping
-            const uint32_t left = n - nd;
-            gp(c.inbox_n)[r] = left;
-            if (!ctr_ok) {
-                if (sS[SC_STATUS] == TW_REP_RUNNING) sc[SC_STATUS] = TW_REP_ERR_COUNTER;
-            } else {
-                sc[SC_SEQ] = s0 + nd + bsum[5];  // the due run's seqs s0 + 1 .. s0 + nd, then the batch's
-            }
-            sc[SC_DUE_SEQ] = s0;
-            sc[SC_DUE_N] = nd;
-            sc[SC_DUE_H] = K;
-            if (c.bat_ctr) {
-                atomicAdd(gp(c.bat_ctr) + 1, (unsigned long long)nd);
-                if (K) atomicAdd(gp(c.bat_ctr), (unsigned long long)K);
-            }
-            if (smin != ~0ull)
-                __hip_atomic_fetch_min(c.rw ? (uint64_t GAS*)rw_at(c, RW_WIN, r) : gp(c.pend_min), (uint64_t)smin,
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (nd) lp_mark(c, r, wid - 1u);
-            if (left) {
-                const uint32_t l = lst ^ 1u;
-                const uint32_t i = __hip_atomic_fetch_add(gp(c.heavy_n) + l, 1u, __ATOMIC_RELAXED,
-                                                          __HIP_MEMORY_SCOPE_AGENT);
-                if (i < c.R) gp(c.heavy)[(size_t)l * c.R + i] = r;
-                else __hip_atomic_fetch_or(gp(c.lp_err), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            // tw_lp_batch's totals, as the prefix's events on the chain add them
-            if (K) {
-                sc[SC_DELIVERED] = sS[SC_DELIVERED] + bsum[0];
-                sc[SC_UNDELIV] = sS[SC_UNDELIV] + bsum[1];
-                sc[SC_DROPPED] = sS[SC_DROPPED] + bsum[2];
-                sc[SC_EVENTS] = sS[SC_EVENTS] + bsum[3];
-                sc[SC_THREADS] = sS[SC_THREADS] + bsum[4];
-                sc[SC_TIDC] = sS[SC_TIDC] + bsum[0];  // (a thread id per handler)
-                if ((int64_t)sS[SC_NOW] < (int64_t)bLast) sc[SC_NOW] = (uint64_t)bLast;
-                if ((int64_t)sS[SC_FINAL_T] < (int64_t)bFin) sc[SC_FINAL_T] = (uint64_t)bFin;
-                if (bH)
-                    __hip_atomic_fetch_add((unsigned long long GAS*)(gp(c.hash_g) + c.lp0 + r), bH, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
-                if (bDirect)
-                    min_hot(c.rw ? (uint64_t GAS*)rw_at(c, RW_WIN, r) : (uint64_t GAS*)(gp(c.win) + WN_REC_MIN),
-                            (uint64_t)(tend + 1));
-            }
-        }
-    }
-}
-// The light lanes tw_lp_due_batch delivered batched replies to, marked for the
-// next window now that this window's list is built; the other parity's list
-// (the window before's, already marked) is emptied for the next window.
-__global__ void __launch_bounds__(256) tw_lp_dmark(Dev c) {
-    const int64_t GAS* w = gp(c.win);
-    const int64_t fl = w[WN_FLAGS];
-    if (!(fl & WN_FRESH) || (fl & WN_DONE)) return;
-    const uint32_t wid = (uint32_t)w[WN_WID], p = wid & 1u;
-    uint32_t n = gp(c.dmk_n)[p];
-    n = n < c.dmk_cap ? n : c.dmk_cap;
-    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
-        lp_mark(c, gp(c.dmk)[(size_t)p * c.dmk_cap + i], wid);
-    if (blockIdx.x == 0 && threadIdx.x == 0) gp(c.dmk_n)[p ^ 1u] = 0;
 }
 
 // Batched LP: a replica's results = its nodes' lanes (lane = node << rep_lg |

@@ -144,7 +144,7 @@ def counted_waits(body):
 def main():
     s = open(sys.argv[1]).read().split("\n")
     if not any(TAG.search(l) for l in s):
-        print("no tagged LDS-DMA loads (a TW_DMA_BUILTIN build?): nothing to check")
+        print("no tagged LDS-DMA loads: nothing to check")
         return 1
     starts = [(i, m.group(1)) for i, l in enumerate(s) if (m := re.match(r"(_ZN12_GLOBAL__N_113tw_run_kernel\S+):", l))]
     slow = bad = 0
