@@ -463,6 +463,26 @@ int tw_tie_audit(tw_ctx* ctx, int64_t t_end_us, uint64_t max_events, uint32_t pr
  * replica's pending events. */
 int tw_set_tie_mode(tw_ctx* ctx, uint32_t mode);
 
+/* Same-time killThread sweeps (replica geometries DENSE, NARROW and HALF
+ * under TW_TIE_FIFO / TW_TIE_FORKFIRST).  When the program image parks threads
+ * with `WAIT_ABS K[imm]` in front of a kill stub (`throwTo r, ThreadKilled`
+ * once or twice, then END: `schedule (at t) (mapM_ killThread [..])`), tw_run
+ * stops every replica just before that time and carries out all of a replica's
+ * kill wakes and victim pops at it in data-parallel kernels instead of one pop
+ * at a time.  A replica is swept only when the result is what the pops would
+ * have left (every event at that time is such a wake of a far run, every
+ * victim is a started, queued, non-main thread with no handler for
+ * ThreadKilled, no `timeout` around it and no exception pending, and the
+ * event cap and the insertion counter have room); any other replica is left
+ * as it was and pops them one by one.  Results, node hashes and statuses are
+ * the same either way.  on != 0 enables it (the default after every tw_load),
+ * 0 disables it for later tw_run calls.  TW_ERR_STATE before tw_load. */
+int tw_set_sweep(tw_ctx* ctx, int on);
+/* Of the last tw_run, summed over the context's devices: kill wakes and
+ * victims retired by sweeps, and replicas that had events at a sweep time but
+ * were refused (they took the sequential path).  Any pointer may be NULL. */
+int tw_sweep_stats(tw_ctx* ctx, uint64_t* killers, uint64_t* victims, uint64_t* refused_replicas);
+
 /* Testing hook: from the next tw_reset on, start every replica's insertion
  * counter at seq0 and its thread counter at tid0 (>= 1; main is tid 0), so the
  * TW_REP_ERR_COUNTER guard can be reached in a short run. */

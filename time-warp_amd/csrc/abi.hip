@@ -670,6 +670,30 @@ int tw_set_tie_mode(tw_ctx* c, uint32_t mode) {
     return TW_OK;
 }
 
+int tw_set_sweep(tw_ctx* c, int on) {
+    if (!c) return TW_ERR_INVALID;
+    for (tw_shard* s : c->sh) {
+        int rc = sh_set_sweep(s, on);
+        if (rc) return rc;
+    }
+    return TW_OK;
+}
+
+int tw_sweep_stats(tw_ctx* c, uint64_t* killers, uint64_t* victims, uint64_t* refused_replicas) {
+    if (!c) return TW_ERR_INVALID;
+    uint64_t k = 0, v = 0, f = 0;
+    for (tw_shard* s : c->sh) {
+        uint64_t a = 0, b = 0, d = 0;
+        int rc = sh_sweep_stats(s, &a, &b, &d, nullptr);
+        if (rc) return rc;
+        k += a; v += b; f += d;
+    }
+    if (killers) *killers = k;
+    if (victims) *victims = v;
+    if (refused_replicas) *refused_replicas = f;
+    return TW_OK;
+}
+
 int tw_geometry(tw_ctx* c) {
     if (!c) return TW_ERR_INVALID;
     return sh_geometry(c->sh[0]);
@@ -1095,6 +1119,11 @@ int tw_lp_run(tw_ctx* c, uint64_t max_ticks, tw_lp_state* out) {
 int tw_prof_read(tw_ctx* c, unsigned long long* out, size_t cap, int reset) {
     if (!c) return TW_ERR_INVALID;
     return sh_prof_read(c->sh[0], out, cap, reset);
+}
+// device time of the last tw_run's sweep kernels (tools/stats_probe.py)
+int tw_sweep_ms(tw_ctx* c, double* ms) {
+    if (!c || !ms) return TW_ERR_INVALID;
+    return sh_sweep_stats(c->sh[0], nullptr, nullptr, nullptr, ms);
 }
 #endif
 

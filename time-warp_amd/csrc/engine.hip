@@ -40,6 +40,8 @@
 #include "../../include/timewarp.h"
 #include "tw_dev.hpp"
 #include "shard.hpp"
+#include "sweep_classify.hpp"
+#include "sweep_dev.hpp"
 
 #include "engine_dev.hpp"
 
@@ -103,6 +105,17 @@ struct tw_shard {
     // for tests: a small budget makes windows take several ticks)
     uint32_t lp_budget = 1u << 14;
     uint32_t lp_grid = TW_LP_GRID;  // LP launches above this many workgroups walk the list (TW_LP_GRID env)
+    // killThread sweeps (sweep.hip): the classifier's tables and the
+    // sweep kernels' scratch (sw.stub null: no kill stub in the image, or no
+    // memory for the scratch), the image's sweep times, which of them were swept
+    // since the last tw_reset, and the last tw_run's counts
+    bool sweep_on = true;
+    tw::SweepTab sw{};
+    std::vector<int64_t> sw_times;
+    uint32_t sw_done = 0;
+    unsigned long long* h_sw = nullptr;  // pinned
+    uint64_t sw_last[3] = {0, 0, 0};
+    double sw_ms = 0.0;                  // device time of the last tw_run's sweeps
     Dev dwin() const {                // the descriptor the device loop's kernels get
         Dev x = d;
         x.win = win_buf;
@@ -163,6 +176,9 @@ void free_all(tw_shard* c) {
     if (c->tick_graph) (void)hipGraphExecDestroy(c->tick_graph);
     c->tick_graph = nullptr;
     c->tick_gkey.clear();
+    c->sw = tw::SweepTab{};
+    c->sw_times.clear();
+    c->sw_done = 0;
     c->loaded = false;
 }
 
@@ -249,6 +265,7 @@ void sh_destroy(tw_shard* c) {
     if (c->h_active) (void)hipHostFree(c->h_active);
     if (c->h_st) (void)hipHostFree(c->h_st);
     if (c->h_win) (void)hipHostFree(c->h_win);
+    if (c->h_sw) (void)hipHostFree(c->h_sw);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -712,6 +729,28 @@ static int load_common(tw_shard* c, const tw_scenario_desc* s, bool lp, uint32_t
             d.lpc_bat = bd;
         }
     }
+    c->sweep_on = true;
+    if (!lp && (c->geo == 0 || c->geo == 2 || c->geo == 5) && d.Cr) {
+        // the far-run geometries: kill stubs and their wake times (sweep_classify.hpp).
+        // The scratch is optional: without it the context runs without sweeps
+        SweepPlan plan = sweep_classify(s->insns, s->n_insns, s->consts, s->n_consts);
+        uint32_t* stub = nullptr;
+        uint32_t* acc = nullptr;
+        unsigned long long* stats = nullptr;
+        if (!plan.times.empty() && (c->h_sw || hipHostMalloc((void**)&c->h_sw, 8 * SWS_COUNT) == hipSuccess) &&
+            dalloc(c, &stub, plan.stub.size()) == TW_OK && dalloc(c, &acc, sweep_acc_words(d.R)) == TW_OK &&
+            dalloc(c, &stats, SWS_COUNT) == TW_OK) {
+            HIPCHK(hipMemcpy(stub, plan.stub.data(), 4 * plan.stub.size(), hipMemcpyHostToDevice));
+            HIPCHK(hipMemsetAsync(stats, 0, 8 * SWS_COUNT, st));
+            c->sw.stub = stub;
+            c->sw.acc = acc;
+            c->sw.stats = stats;
+            c->sw.near_cap = TW_NEAR_CAP;
+            c->sw_times = plan.times;
+        } else {
+            (void)hipGetLastError();  // (a failed allocation is not an error of the load)
+        }
+    }
     d.insns = insns; d.consts = consts; d.lpc = lpc; d.out_off = out_off; d.link_dst = ldst; d.link_rev = lrev;
     d.link_table = ltab;
     c->main_pc = s->main_pc;
@@ -745,6 +784,7 @@ int sh_reset(tw_shard* c) {
     const Dev& d = c->d;
     const size_t R = d.R;
     hipStream_t st = c->stream;
+    c->sw_done = 0;
     HIPCHK(hipMemsetAsync(d.nvars, 0, 32ull * d.N * R, st));
     HIPCHK(hipMemsetAsync(d.hash, 0, 8ull * d.N * R, st));
     HIPCHK(hipMemsetAsync(d.bind, 0, 4ull * d.N * R, st));
@@ -833,8 +873,34 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
     uint32_t launches = 0;
     double kms = 0.0;
     bool quiet = false;
+    // killThread sweeps: the run is split at every sweep time T of
+    // the image that lies within it.  While such a stop is ahead, the event
+    // kernel runs to T - 1 (its "parked beyond t_end" path) and every launch is
+    // followed by the sweep kernels, which fire once, on the device's own
+    // evidence: behind the launch that left every replica parked.  They carry
+    // out the kill wakes and victim pops at T of every replica that qualifies;
+    // replicas they refuse pop them one by one when the event kernel goes on.
+    // No launch and no host round trip is added to a run whose replicas all
+    // end in the sweep (C3): the segment's remaining launches find nothing to
+    // do, and the sweep reports that no replica has work left.
+    struct Stop { int64_t T; uint32_t ix; };
+    std::vector<Stop> stops;
+    c->sw_last[0] = c->sw_last[1] = c->sw_last[2] = 0;
+    c->sw_ms = 0.0;
+    if (!c->lp && c->sweep_on && c->sw.stub && (c->geo == 0 || c->geo == 2 || c->geo == 5) &&
+        (d.tie_mode == TW_TIE_FIFO || d.tie_mode == TW_TIE_FORKFIRST)) {
+        for (uint32_t i = 0; i < c->sw_times.size(); ++i) {
+            const int64_t T = c->sw_times[i];
+            if (T >= 1 && T <= t_end_us && !((c->sw_done >> i) & 1u)) stops.push_back(Stop{T, i});
+        }
+        if (!stops.empty()) HIPCHK(hipMemsetAsync(c->sw.stats, 0, 8 * SWS_COUNT, st));
+    }
+    const size_t sw_ev0 = 2 * (size_t)per_check;  // the sweeps' event pairs, after the launches'
+    size_t seg = 0;
     for (int round = 0; round < (1 << 20); ++round) {
-        size_t need = 2 * per_check;
+        const bool to_sweep = seg < stops.size();
+        const int64_t te_seg = to_sweep ? stops[seg].T - 1 : t_end_us;
+        size_t need = 4 * (size_t)per_check;
         while (c->ev_pool.size() < need) {
             hipEvent_t e;
             HIPCHK(hipEventCreate(&e));
@@ -845,30 +911,54 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
             if (c->lp) HIPCHK(hipMemsetAsync(d.next_t, 0xFF, 8, st));
             HIPCHK(hipEventRecord(c->ev_pool[2 * i], st));
             if (c->lp)
-                launch_run<true, TW_WG_LP, TW_NEAR_LP>(c, st, t_end_us, limit, budget);
+                launch_run<true, TW_WG_LP, TW_NEAR_LP>(c, st, te_seg, limit, budget);
             else if (c->geo == 3)
-                HIPCHK(wave_launch(c->d, c->d_dev, st, t_end_us, limit, 1u << 16));
+                HIPCHK(wave_launch(c->d, c->d_dev, st, te_seg, limit, 1u << 16));
             else if (c->geo == 1)
-                launch_run<false, TW_WG_SPARSE, TW_NEAR_SPARSE>(c, st, t_end_us, limit, budget);
+                launch_run<false, TW_WG_SPARSE, TW_NEAR_SPARSE>(c, st, te_seg, limit, budget);
             else if (c->geo == 2)
-                launch_run<false, TW_WG, TW_NEAR_CAP, TW_HALF_LANES>(c, st, t_end_us, limit, budget);
+                launch_run<false, TW_WG, TW_NEAR_CAP, TW_HALF_LANES>(c, st, te_seg, limit, budget);
             else if (c->geo == 5)
-                launch_run<false, TW_NARROW, TW_NEAR_CAP, TW_NARROW>(c, st, t_end_us, limit, budget);
+                launch_run<false, TW_NARROW, TW_NEAR_CAP, TW_NARROW>(c, st, te_seg, limit, budget);
             else if (c->geo == 7)
-                launch_run<false, TW_WG, TW_NEAR_COMPACT, 64, false>(c, st, t_end_us, limit, budget);
+                launch_run<false, TW_WG, TW_NEAR_COMPACT, 64, false>(c, st, te_seg, limit, budget);
             else
-                launch_run<false, TW_WG, TW_NEAR_CAP>(c, st, t_end_us, limit, budget);
+                launch_run<false, TW_WG, TW_NEAR_CAP>(c, st, te_seg, limit, budget);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(c->ev_pool[2 * i + 1], st));
             ++launches;
+            if (to_sweep) {
+                HIPCHK(hipEventRecord(c->ev_pool[sw_ev0 + 2 * i], st));
+                HIPCHK(sweep_launch(c->d, c->sw, st, stops[seg].T, limit, t_end_us, (uint32_t)seg));
+                HIPCHK(hipEventRecord(c->ev_pool[sw_ev0 + 2 * i + 1], st));
+            }
         }
         HIPCHK(hipMemcpyAsync(c->h_active, d.n_active, 4, hipMemcpyDeviceToHost, st));
+        if (to_sweep) HIPCHK(hipMemcpyAsync(c->h_sw, c->sw.stats, 8 * SWS_COUNT, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         for (int i = 0; i < per_check; ++i) {
             float ms = 0.f;
             HIPCHK(hipEventElapsedTime(&ms, c->ev_pool[2 * i], c->ev_pool[2 * i + 1]));
             c->launch_ms.push_back(ms);
             kms += ms;
+            if (to_sweep) {
+                // (the sweep kernels behind this launch, fired or not: device time of the
+                // step, listed with the launches; `launches` counts the event kernel's)
+                HIPCHK(hipEventElapsedTime(&ms, c->ev_pool[sw_ev0 + 2 * i], c->ev_pool[sw_ev0 + 2 * i + 1]));
+                c->launch_ms.push_back(ms);
+                kms += ms;
+                c->sw_ms += ms;
+            }
+        }
+        if (to_sweep) {
+            if (c->h_sw[SWS_FIRED] > seg) {
+                c->sw_done |= 1u << stops[seg].ix;
+                for (int k = 0; k < 3; ++k) c->sw_last[k] = c->h_sw[k];
+                ++seg;
+                // the last stop swept and no replica has work left before t_end: done
+                if (seg == stops.size() && c->h_sw[SWS_LEFT] == 0) { quiet = true; break; }
+            }
+            continue;
         }
         if (*c->h_active == 0) { quiet = true; break; }
     }
@@ -1014,6 +1104,25 @@ int sh_set_counter_base(tw_shard* c, uint32_t seq0, uint32_t tid0) {
     if (!c || tid0 == 0) return TW_ERR_INVALID;
     c->seq0 = seq0;
     c->tid0 = tid0;
+    return TW_OK;
+}
+
+// The killThread sweep of later tw_run calls (include/timewarp.h tw_set_sweep);
+// on after every tw_load.
+int sh_set_sweep(tw_shard* c, int on) {
+    if (!c) return TW_ERR_INVALID;
+    if (!c->loaded) return TW_ERR_STATE;
+    c->sweep_on = on != 0;
+    return TW_OK;
+}
+
+int sh_sweep_stats(tw_shard* c, uint64_t* killers, uint64_t* victims, uint64_t* refused, double* ms) {
+    if (!c) return TW_ERR_INVALID;
+    if (!c->loaded) return TW_ERR_STATE;
+    if (killers) *killers = c->sw_last[0];
+    if (victims) *victims = c->sw_last[1];
+    if (refused) *refused = c->sw_last[2];
+    if (ms) *ms = c->sw_ms;
     return TW_OK;
 }
 

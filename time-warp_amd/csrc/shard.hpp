@@ -32,6 +32,10 @@ TW_HIDDEN int sh_tie_audit(tw_shard* c, int64_t t_end_us, uint64_t max_events, u
 TW_HIDDEN int sh_geometry(tw_shard* c);
 TW_HIDDEN int sh_set_counter_base(tw_shard* c, uint32_t seq0, uint32_t tid0);
 TW_HIDDEN int sh_set_tie_mode(tw_shard* c, uint32_t mode);
+// killThread sweeps (sweep.hip): the switch, and the last sh_run's counts with
+// the sweep kernels' device time
+TW_HIDDEN int sh_set_sweep(tw_shard* c, int on);
+TW_HIDDEN int sh_sweep_stats(tw_shard* c, uint64_t* killers, uint64_t* victims, uint64_t* refused, double* ms);
 TW_HIDDEN int sh_set_trace(tw_shard* c, uint32_t cap);
 TW_HIDDEN int sh_read_trace(tw_shard* c, uint32_t replica, tw_trace_rec* out, size_t cap, uint64_t* n_emitted);
 // tw_measure on one shard: sh_measure_state is its state check alone

@@ -1,0 +1,355 @@
+// sweep.hip — same-time killThread sweeps as data-parallel kernels.
+//
+// C3's teardown is, per replica, 4,097 kill wakes `throwTo r1; throwTo r2; END`
+// at one absolute time T and the 8,194 victim pops behind them: a serial chain
+// of ~12.3k pops on the event loop's one lane per replica.  The host stops
+// every replica just before a statically known sweep time (sh_run runs the
+// event kernel to T - 1 first) and these kernels carry out all the pops at T
+// of a replica at once, over the state the event kernel's epilogue persisted.
+// Lanes are 64 consecutive replicas (the replica-minor arrays coalesce); a
+// replica's entries are dealt to gridDim.y waves.
+//
+//   scan      per replica: is every event at T in a prefix of the far runs?
+//             (prefix lengths by binary search: runs are monotone)
+//   validate  read-only, per entry: a live kill-stub wake whose refs are stale
+//             or name plain victims (see below); counts killers and throwTos
+//   apply     per entry, replicas that passed: what the pops would have left
+//   finalize  per replica: the scalar words, run heads, free-stack top
+//
+// A replica that fails any check is left exactly as it was and takes the
+// event kernel's sequential path.  Plain C++ and vector atomics only.
+#include <hip/hip_runtime.h>
+
+#include "tw_dev.hpp"
+#include "sweep_dev.hpp"
+#include "sweep_classify.hpp"
+
+namespace {
+
+using namespace tw;
+
+__device__ __forceinline__ uint32_t GAS* acc_at(const SweepTab& t, const Dev& c, int w, uint32_t r) {
+    return gp(t.acc) + (size_t)w * c.R + r;
+}
+__device__ __forceinline__ uint4 GAS* run_ent(const Dev& c, uint32_t j, uint32_t pos, uint32_t r) {
+    return gp(c.runs) + ((size_t)j * c.Cr + pos) * c.R + r;
+}
+__device__ __forceinline__ uint4 GAS* rec_q(const Dev& c, uint32_t slot, uint32_t r, uint32_t q) {
+    return gp(c.slots) + (size_t)q * c.RQ + (size_t)slot * c.R + r;
+}
+__device__ __forceinline__ uint32_t seq_limit(const Dev& c) {
+    return c.tie_mode == TW_TIE_FORKFIRST ? 0x7FFFFFFFu : 0xFFFFFFFFu;
+}
+// The sweep of stop `expect` runs once, right after the event-kernel launch
+// that left every replica parked (n_active == 0: the launch's count of lanes
+// that still had something to do before its t_end).  The host enqueues it
+// after every launch of the segment; the others leave here.
+__device__ __forceinline__ bool sweep_gate(const Dev& c, const SweepTab& t, uint32_t expect) {
+    return *gp(c.n_active) == 0u && gp(t.stats)[SWS_FIRED] == (unsigned long long)expect;
+}
+// register i of a record from its register quads
+__device__ __forceinline__ uint64_t reg_of(uint4 q2, uint4 q3, uint32_t i) {
+    const uint32_t lo = i == 0 ? q2.x : i == 1 ? q2.z : i == 2 ? q3.x : q3.z;
+    const uint32_t hi = i == 0 ? q2.y : i == 1 ? q2.w : i == 2 ? q3.y : q3.w;
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// ---------------------------------------------------------------------- scan
+__global__ void __launch_bounds__(256) tw_sweep_scan(Dev c, SweepTab t, int64_t T, uint32_t expect) {
+    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= c.R || !sweep_gate(c, t, expect)) return;
+    const size_t R = c.R;
+    const uint64_t GAS* sc = gp(c.scal) + r;
+    for (int w = 0; w < SW_COUNT; ++w) *acc_at(t, c, w, r) = 0u;
+    const bool att = sc[SC_STATUS * R] == TW_REP_RUNNING && sc[SC_PENDING_MAIN * R] == 0 && sc[SC_LIVE * R] != 0 &&
+                     c.Cr != 0;
+    if (!att) { *acc_at(t, c, SW_BAD, r) = 2u; return; }
+    // the earliest event outside the runs: near spill, far-heap top
+    int64_t other = INT64_MAX;
+    uint32_t nn = (uint32_t)sc[SC_NEAR_N * R];
+    const bool spill_ok = nn <= t.near_cap;
+    nn = spill_ok ? nn : 0u;
+    for (uint32_t j = 0; j < nn; ++j) {
+        const int64_t x = ent_t(gp(c.near_spill)[(size_t)j * R + r]);
+        other = x < other ? x : other;
+    }
+    if ((uint32_t)sc[SC_FAR_N * R]) {
+        const int64_t x = ent_t(gp(c.far)[r]);
+        other = x < other ? x : other;
+    }
+    int64_t rmin = INT64_MAX;
+    uint32_t pl[TW_RUNS];
+    for (uint32_t j = 0; j < TW_RUNS; ++j) {
+        const uint32_t rh = (uint32_t)sc[(SC_RH0 + j) * R], rn = (uint32_t)sc[(SC_RC0 + j) * R];
+        pl[j] = 0;
+        if (rn == 0 || rn > c.Cr || rh >= c.Cr) continue;
+        const int64_t h = ent_t(*run_ent(c, j, rh, r));
+        rmin = h < rmin ? h : rmin;
+        uint32_t lo = 0, hi = rn;  // entries [0, lo) are at <= T
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            uint32_t pos = rh + mid;
+            pos = pos >= c.Cr ? pos - c.Cr : pos;
+            if (ent_t(*run_ent(c, j, pos, r)) <= T) lo = mid + 1;
+            else hi = mid;
+        }
+        pl[j] = lo;
+    }
+    const int64_t first = other < rmin ? other : rmin;
+    {   // for finalize's count of replicas with work left: the next event of a
+        // replica that is not attempted, or the next one outside the runs
+        const int64_t x = (first == T && other > T && spill_ok) ? other : first;
+        *acc_at(t, c, SW_XLO, r) = (uint32_t)x;
+        *acc_at(t, c, SW_XHI, r) = (uint32_t)((uint64_t)x >> 32);
+    }
+    if (first != T) { *acc_at(t, c, SW_BAD, r) = 2u; return; }  // nothing at T (or stopped short of it)
+    if (other <= T || !spill_ok) { *acc_at(t, c, SW_BAD, r) = 1u; return; }
+    for (uint32_t j = 0; j < TW_RUNS; ++j) *acc_at(t, c, SW_PL0 + j, r) = pl[j];
+    // the register-cached top of the free stack goes to its place in memory:
+    // apply appends behind it (position free_n - 1 is unused while the top is cached)
+    const uint32_t fn = (uint32_t)sc[SC_FREE_N * R];
+    if (fn != 0 && fn <= c.S) gp(c.free_stk)[(size_t)(fn - 1) * R + r] = (uint32_t)sc[SC_FTOP * R];
+}
+
+// what both per-entry kernels read of a prefix entry's killer
+struct Killer {
+    uint4 h;       // header quad
+    uint32_t sw;   // stub word of its resume pc
+    uint64_t ref0, ref1;  // its victims' refs (ref1: of a stub with two throwTos)
+    uint32_t nref;
+};
+
+__device__ __forceinline__ bool load_killer(const Dev& c, const SweepTab& t, uint32_t r, uint4 e, int64_t T, Killer& k) {
+    k.nref = 0;
+    k.sw = 0;
+    if (ent_t(e) != T || e.z >= c.S) return false;
+    k.h = *rec_q(c, e.z, r, 0);
+    const uint32_t pc = k.h.x & 0xFFFFu;
+    k.sw = gp(t.stub)[pc < c.n_insns ? pc : c.n_insns];
+    const uint32_t fl = (k.h.x >> FL_SHIFT) & 0x3Fu;
+    // live, no exception pending, a kill-stub entry, not main, no frames
+    if (k.h.w != e.w || (k.h.x >> EXC_SHIFT) != 0 || !(k.sw & SWB_VALID) || (fl & F_MAIN) || ((k.h.x >> 16) & 15u) != 0 ||
+        k.h.y >= c.N)
+        return false;
+    const uint32_t a0 = SWB_RA0(k.sw), a1 = SWB_RA1(k.sw);
+    const bool two = (k.sw & SWB_TWO) != 0;
+    const bool n2 = a0 < 2 || (two && a1 < 2), n3 = a0 >= 2 || (two && a1 >= 2);
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    const uint4 q2 = n2 ? *rec_q(c, e.z, r, 2) : z, q3 = n3 ? *rec_q(c, e.z, r, 3) : z;
+    k.ref0 = reg_of(q2, q3, a0);
+    k.ref1 = two ? reg_of(q2, q3, a1) : 0ull;
+    k.nref = two ? 2u : 1u;
+    return true;
+}
+
+// a dying thread's owned listener is released by one store (Lane::rel_bind);
+// with several dying owners of one node the last store would win, so only the
+// node's current owner may die in a sweep
+__device__ __forceinline__ bool owner_ok(const Dev& c, uint32_t r, uint4 h) {
+    if (!(((h.x >> FL_SHIFT) & 0x3Fu) & F_OWNS)) return true;
+    return gp(c.bind_own)[(size_t)h.y * c.R + r] == h.z;
+}
+
+// ------------------------------------------------------------------ validate
+__global__ void __launch_bounds__(64) tw_sweep_validate(Dev c, SweepTab t, int64_t T, uint32_t expect) {
+    const uint32_t r = blockIdx.x * 64 + threadIdx.x;
+    if (r >= c.R || !sweep_gate(c, t, expect)) return;
+    if (*acc_at(t, c, SW_BAD, r)) return;
+    const size_t R = c.R;
+    const uint64_t GAS* sc = gp(c.scal) + r;
+    uint32_t nk = 0, nh = 0;
+    bool bad = false;
+    for (uint32_t j = 0; j < TW_RUNS && !bad; ++j) {
+        const uint32_t pl = *acc_at(t, c, SW_PL0 + j, r), rh = (uint32_t)sc[(SC_RH0 + j) * R];
+        for (uint32_t i = blockIdx.y; i < pl && !bad; i += gridDim.y) {
+            uint32_t pos = rh + i;
+            pos = pos >= c.Cr ? pos - c.Cr : pos;
+            Killer k;
+            if (!load_killer(c, t, r, *run_ent(c, j, pos, r), T, k) || !owner_ok(c, r, k.h)) { bad = true; break; }
+            ++nk;
+#pragma unroll
+            for (uint32_t v = 0; v < 2; ++v) {
+                if (v >= k.nref) break;
+                const uint64_t ref = v ? k.ref1 : k.ref0;
+                const uint32_t ts = (uint32_t)ref, tid = (uint32_t)(ref >> 32);
+                if (ts >= c.S) continue;                      // a stale ref: no-op (Lane::throw_to)
+                const uint4 h = *rec_q(c, ts, r, 0);
+                if (h.z != tid) continue;                     // dead: slot free or reused
+                const uint32_t fl = (h.x >> FL_SHIFT) & 0x3Fu, nfr = (h.x >> 16) & 15u, pc = h.x & 0xFFFFu;
+                bool ok = (fl & F_STARTED) && !(fl & F_MAIN) && (h.x >> EXC_SHIFT) == 0 && nfr <= 2 && h.w != 0 &&
+                          h.y < c.N && gp(t.stub)[pc < c.n_insns ? pc : c.n_insns] == 0 && owner_ok(c, r, h);
+                if (ok && nfr) {
+                    // neither a finally frame (mask 0) nor one catching ThreadKilled
+                    const uint4 f = *rec_q(c, ts, r, 1);
+                    const uint32_t m0 = f.x >> 16, m1 = nfr > 1 ? f.y >> 16 : 0xFFFFu;
+                    ok = m0 != 0 && m1 != 0 && !((m0 | (nfr > 1 ? m1 : 0u)) & (1u << TW_EXC_THREAD_KILLED));
+                }
+                if (!ok) { bad = true; break; }
+                ++nh;
+            }
+        }
+    }
+    if (bad) {
+        __hip_atomic_fetch_or(acc_at(t, c, SW_BAD, r), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else if (nk) {
+        __hip_atomic_fetch_add(acc_at(t, c, SW_K, r), nk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (nh) __hip_atomic_fetch_add(acc_at(t, c, SW_H, r), nh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// The replica passed validation and the sweep fits its caps.  Every pop of the
+// sweep is an event and every throwTo that hits a live victim takes a seq
+// (Lane::throw_to's re-stamp).  The victims are counted once per throwTo here
+// (two killers naming one victim: an upper bound of the distinct victims), so
+// a sweep that only just fits the event cap may be refused: never the reverse.
+__device__ __forceinline__ bool sweep_go(const Dev& c, const SweepTab& t, uint32_t r, uint64_t max_events) {
+    if (*acc_at(t, c, SW_BAD, r)) return false;
+    const uint64_t k = *acc_at(t, c, SW_K, r), h = *acc_at(t, c, SW_H, r);
+    const uint64_t ev = gp(c.scal)[(size_t)SC_EVENTS * c.R + r], sq = gp(c.scal)[(size_t)SC_SEQ * c.R + r];
+    return k != 0 && ev + k + h <= max_events && sq + h < (uint64_t)seq_limit(c);
+}
+
+// --------------------------------------------------------------------- apply
+__global__ void __launch_bounds__(64) tw_sweep_apply(Dev c, SweepTab t, int64_t T, uint64_t max_events,
+                                                      uint32_t expect) {
+    const uint32_t r = blockIdx.x * 64 + threadIdx.x;
+    if (r >= c.R || !sweep_gate(c, t, expect)) return;
+    if (!sweep_go(c, t, r, max_events)) return;
+    const size_t R = c.R;
+    const uint64_t GAS* sc = gp(c.scal) + r;
+    const uint32_t fn0 = (uint32_t)sc[SC_FREE_N * R];
+    const uint64_t vterm = term0(T, TW_KIND_EXC | TW_EXC_THREAD_KILLED);
+    uint32_t nv = 0;
+    for (uint32_t j = 0; j < TW_RUNS; ++j) {
+        const uint32_t pl = *acc_at(t, c, SW_PL0 + j, r), rh = (uint32_t)sc[(SC_RH0 + j) * R];
+        for (uint32_t i = blockIdx.y; i < pl; i += gridDim.y) {
+            uint32_t pos = rh + i;
+            pos = pos >= c.Cr ? pos - c.Cr : pos;
+            const uint4 e = *run_ent(c, j, pos, r);
+            Killer k;
+            if (!load_killer(c, t, r, e, T, k)) continue;  // (validated: cannot happen)
+            // the kill wake's pop: its resume term, then END (Lane::die_prep)
+            __hip_atomic_fetch_add((unsigned long long GAS*)(gp(c.hash) + (size_t)k.h.y * R + r),
+                                   (unsigned long long)term0(T, TW_KIND_RESUME | (k.h.x & 0xFFFFu)), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+            if (((k.h.x >> FL_SHIFT) & 0x3Fu) & F_OWNS) gp(c.bind_rel)[(size_t)k.h.y * R + r] = k.h.z;
+            *rec_q(c, e.z, r, 0) = make_uint4(k.h.x | (F_STARTED << FL_SHIFT), k.h.y, 0xFFFFFFFFu, 0u);
+            // the victim dies once: whoever takes its queued seq owns its pop
+            auto claim = [&](uint64_t ref) -> bool {
+                const uint32_t ts = (uint32_t)ref, tid = (uint32_t)(ref >> 32);
+                if (ts >= c.S) return false;
+                uint4 GAS* hp = rec_q(c, ts, r, 0);
+                const uint4 h = *hp;
+                if (h.z != tid) return false;  // stale, or claimed by another killer already
+                const uint32_t old = __hip_atomic_exchange((uint32_t GAS*)hp + 3, 0u, __ATOMIC_RELAXED,
+                                                           __HIP_MEMORY_SCOPE_AGENT);
+                if (old == 0) return false;
+                ((uint32_t GAS*)hp)[2] = 0xFFFFFFFFu;
+                __hip_atomic_fetch_add((unsigned long long GAS*)(gp(c.hash) + (size_t)h.y * R + r),
+                                       (unsigned long long)vterm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (((h.x >> FL_SHIFT) & 0x3Fu) & F_OWNS) gp(c.bind_rel)[(size_t)h.y * R + r] = tid;
+                return true;
+            };
+            const bool c0 = claim(k.ref0);
+            const bool c1 = k.nref > 1 && claim(k.ref1);
+            const uint32_t nf = 1u + (c0 ? 1u : 0u) + (c1 ? 1u : 0u);
+            nv += nf - 1u;
+            // the freed slots go onto the free stack, behind what it held
+            const uint32_t at = fn0 + __hip_atomic_fetch_add(acc_at(t, c, SW_FREE, r), nf, __ATOMIC_RELAXED,
+                                                             __HIP_MEMORY_SCOPE_AGENT);
+            if (at < c.S) gp(c.free_stk)[(size_t)at * R + r] = e.z;
+            if (c0 && at + 1u < c.S) gp(c.free_stk)[(size_t)(at + 1u) * R + r] = (uint32_t)k.ref0;
+            if (c1 && at + nf - 1u < c.S) gp(c.free_stk)[(size_t)(at + nf - 1u) * R + r] = (uint32_t)k.ref1;
+        }
+    }
+    if (nv) __hip_atomic_fetch_add(acc_at(t, c, SW_V, r), nv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ------------------------------------------------------------------ finalize
+__global__ void __launch_bounds__(256) tw_sweep_finalize(Dev c, SweepTab t, int64_t T, uint64_t max_events,
+                                                          int64_t t_end, uint32_t expect) {
+    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+    if (!sweep_gate(c, t, expect)) return;
+    unsigned long long k = 0, v = 0, ref = 0, rem = 0;
+    if (r < c.R) {
+        const size_t R = c.R;
+        uint64_t GAS* sc = gp(c.scal) + r;
+        const uint32_t bad = *acc_at(t, c, SW_BAD, r);
+        // the replica's next event, for the count of replicas a later launch has work for
+        int64_t next = (int64_t)(((uint64_t)*acc_at(t, c, SW_XHI, r) << 32) | *acc_at(t, c, SW_XLO, r));
+        if (sweep_go(c, t, r, max_events)) {
+            k = *acc_at(t, c, SW_K, r);
+            v = *acc_at(t, c, SW_V, r);
+            const uint32_t h = *acc_at(t, c, SW_H, r), m = *acc_at(t, c, SW_FREE, r);
+            sc[SC_EVENTS * R] += k + v;
+            sc[SC_NOW * R] = (uint64_t)T;
+            sc[SC_FINAL_T * R] = (uint64_t)T;
+            const uint64_t live = sc[SC_LIVE * R] - (k + v);
+            sc[SC_LIVE * R] = live;
+            sc[SC_SEQ * R] += h;
+            const uint32_t fn = (uint32_t)sc[SC_FREE_N * R] + m;
+            sc[SC_FREE_N * R] = fn;
+            if (fn != 0 && fn <= c.S) sc[SC_FTOP * R] = gp(c.free_stk)[(size_t)(fn - 1) * R + r];
+            for (uint32_t j = 0; j < TW_RUNS; ++j) {
+                const uint32_t pl = *acc_at(t, c, SW_PL0 + j, r);
+                uint32_t rh = (uint32_t)sc[(SC_RH0 + j) * R] + pl;
+                rh = rh >= c.Cr ? rh - c.Cr : rh;
+                sc[(SC_RH0 + j) * R] = rh;
+                const uint64_t left = sc[(SC_RC0 + j) * R] - pl;
+                sc[(SC_RC0 + j) * R] = left;
+                if (left) {
+                    const int64_t x = ent_t(*run_ent(c, j, rh, r));
+                    next = x < next ? x : next;
+                }
+            }
+            if (live == 0) sc[SC_STATUS * R] = TW_REP_DONE;  // whileM_ notDone (TimedT.hs:239)
+        } else if (bad != 2u) {
+            ref = 1;
+            next = T;
+        }
+        // (the event kernel's own rule for a lane it counts in n_active)
+        if (sc[SC_STATUS * R] == TW_REP_RUNNING &&
+            (sc[SC_PENDING_MAIN * R] != 0 || sc[SC_LIVE * R] == 0 || (sc[SC_EVENTS * R] < max_events && next <= t_end)))
+            rem = 1;
+    }
+    for (int m = 32; m >= 1; m >>= 1) {
+        k += __shfl_xor(k, m, 64);
+        v += __shfl_xor(v, m, 64);
+        ref += __shfl_xor(ref, m, 64);
+        rem += __shfl_xor(rem, m, 64);
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        if (k) __hip_atomic_fetch_add(gp(t.stats) + 0, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (v) __hip_atomic_fetch_add(gp(t.stats) + 1, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (ref) __hip_atomic_fetch_add(gp(t.stats) + 2, ref, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (rem) __hip_atomic_fetch_add(gp(t.stats) + SWS_LEFT, rem, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// the stop is done (a kernel of its own: every block of finalize reads the gate)
+__global__ void tw_sweep_mark(Dev c, SweepTab t, uint32_t expect) {
+    if (sweep_gate(c, t, expect)) gp(t.stats)[SWS_FIRED] = (unsigned long long)expect + 1ull;
+}
+
+}  // namespace
+
+namespace tw {
+
+size_t sweep_acc_words(uint32_t R) { return (size_t)SW_COUNT * R; }
+
+hipError_t sweep_launch(const Dev& d, const SweepTab& t, hipStream_t st, int64_t T, uint64_t max_events, int64_t t_end,
+                        uint32_t expect) {
+    const uint32_t groups = (d.R + 63u) / 64u;
+    // a replica's entries over enough waves to fill the GPU (256 CUs x 8 waves and more)
+    uint32_t chunks = 131072u / groups;
+    chunks = chunks < 16u ? 16u : chunks > 256u ? 256u : chunks;
+    const dim3 gr((d.R + 255u) / 256u), ge(groups, chunks);
+    hipLaunchKernelGGL(tw_sweep_scan, gr, dim3(256), 0, st, d, t, T, expect);
+    hipLaunchKernelGGL(tw_sweep_validate, ge, dim3(64), 0, st, d, t, T, expect);
+    hipLaunchKernelGGL(tw_sweep_apply, ge, dim3(64), 0, st, d, t, T, max_events, expect);
+    hipLaunchKernelGGL(tw_sweep_finalize, gr, dim3(256), 0, st, d, t, T, max_events, t_end, expect);
+    hipLaunchKernelGGL(tw_sweep_mark, dim3(1), dim3(1), 0, st, d, t, expect);
+    return hipGetLastError();
+}
+
+}  // namespace tw

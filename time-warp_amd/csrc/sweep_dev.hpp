@@ -1,0 +1,39 @@
+// sweep_dev.hpp — what engine.hip and sweep.hip share of the killThread sweep
+// (DESIGN §3l): the sweep kernels' own tables, passed as a kernel argument
+// of their own (Dev, the event kernels' argument, is unchanged).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "tw_dev.hpp"
+
+namespace tw {
+
+// per-replica accumulator words, [SW_*][R] u32, cleared by the scan:
+// SW_BAD 0 swept so far / 1 refused / 2 nothing to sweep; killers, throwTos
+// that hit a live victim, victims claimed, slots freed, the replica's next
+// event outside the swept prefixes (two words), prefix length per run
+enum { SW_BAD, SW_K, SW_H, SW_V, SW_FREE, SW_XLO, SW_XHI, SW_PL0, SW_COUNT = SW_PL0 + TW_RUNS };
+// Sweep words of a tw_run, SweepTab::stats: kill wakes, victims and refused
+// replicas; how many of the run's stops have been swept; replicas a later
+// launch still has work for, as of the last sweep
+enum { SWS_KILLERS, SWS_VICTIMS, SWS_REFUSED, SWS_FIRED, SWS_LEFT, SWS_COUNT };
+
+struct SweepTab {
+    const uint32_t* stub;       // [n_insns + 1] stub word of each resume pc (sweep_classify.hpp)
+    uint32_t* acc;              // [SW_COUNT][R]
+    unsigned long long* stats;  // [SWS_COUNT]
+    uint32_t near_cap;          // entries of the near spill per replica
+};
+
+size_t sweep_acc_words(uint32_t R);
+// The sweep at time T of the run's stop number `expect`, on stream st, behind an
+// event-kernel launch to T - 1: it runs if that launch left every replica
+// parked and the stop has not been swept yet, and is a handful of empty
+// kernels otherwise.  t_end: the run's, for the count of replicas with work left.
+hipError_t sweep_launch(const Dev& d, const SweepTab& t, hipStream_t st, int64_t T, uint64_t max_events, int64_t t_end,
+                        uint32_t expect);
+
+}  // namespace tw

@@ -31,7 +31,7 @@ EXPORTS = ["tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_ru
            "tw_set_trace", "tw_read_trace", "tw_tie_audit", "tw_set_counter_base", "tw_geometry",
            "tw_set_stream", "tw_lp_exchange_setup", "tw_lp_loop_begin", "tw_lp_tick", "tw_lp_tick_import",
            "tw_lp_tick_end", "tw_lp_progress", "tw_lp_run_windows", "tw_lpb_load", "tw_lpb_windows",
-           "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms"]
+           "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms", "tw_set_sweep", "tw_sweep_stats"]
 GEOMETRIES = ("dense", "sparse", "half", "wave", "lp", "narrow", "lpb", "compact")  # TW_GEO_* order
 
 # tw_trace_rec (include/timewarp.h)
@@ -110,12 +110,15 @@ def load_library(path: Optional[str] = None):
     lib.tw_measure.argtypes = [C.c_void_p, C.POINTER(TwMeasureSpec), C.POINTER(TwMeasureOut), C.c_void_p, C.c_void_p,
                                C.c_size_t]
     lib.tw_measure_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.tw_set_sweep.argtypes = [C.c_void_p, C.c_int]
+    lib.tw_sweep_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
     for name in ("tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_run", "tw_set_tie_mode", "tw_load", "tw_reset", "tw_run", "tw_read_results", "tw_read_hashes", "tw_read_final",
                  "tw_last_launch_ms", "tw_lp_load", "tw_lp_window", "tw_lp_take_outbox", "tw_lp_inject",
                  "tw_lp_results", "tw_set_trace", "tw_read_trace", "tw_tie_audit", "tw_set_counter_base",
                  "tw_geometry", "tw_set_stream", "tw_lp_exchange_setup", "tw_lp_loop_begin", "tw_lp_tick",
                  "tw_lp_tick_import", "tw_lp_tick_end", "tw_lp_progress", "tw_lp_run_windows", "tw_lpb_load",
-                 "tw_lpb_windows", "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms"):
+                 "tw_lpb_windows", "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms", "tw_set_sweep",
+                 "tw_sweep_stats"):
         getattr(lib, name).restype = C.c_int
     if path is None:
         _lib = lib
@@ -333,6 +336,20 @@ class Engine:
         replica geometries only."""
         _check(self.lib.tw_set_tie_mode(self.ctx, self.TIE_MODES[mode]), "tw_set_tie_mode")
         return self
+
+    def set_sweep(self, on: bool) -> "Engine":
+        """Same-time killThread sweeps of later runs (tw_set_sweep): on after
+        every load; off makes every kill wake and victim take the event
+        kernel's one-pop-at-a-time path.  Results are the same either way."""
+        _check(self.lib.tw_set_sweep(self.ctx, 1 if on else 0), "tw_set_sweep")
+        return self
+
+    def sweep_stats(self) -> dict:
+        """Of the last run: kill wakes and victims retired by sweeps, and
+        replicas with events at a sweep time that were refused (tw_sweep_stats)."""
+        k, v, f = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(self.lib.tw_sweep_stats(self.ctx, C.byref(k), C.byref(v), C.byref(f)), "tw_sweep_stats")
+        return {"killers": int(k.value), "victims": int(v.value), "refused_replicas": int(f.value)}
 
     def set_counter_base(self, seq0: int, tid0: int = 1) -> "Engine":
         """Testing hook: start the 32-bit insertion / thread counters at these

@@ -106,6 +106,8 @@ def main():
     eng = Engine(0).load(scn)
     if os.environ.get("TW_PROBE_TIE"):  # e.g. forkfirst (bench.py's C3 order)
         eng.set_tie_mode(os.environ["TW_PROBE_TIE"])
+    if os.environ.get("TW_PROBE_SWEEP") == "0":  # the teardown one pop at a time (DESIGN 3l's "before")
+        eng.set_sweep(False)
     if not hasattr(eng.lib, "tw_prof_read"):
         raise SystemExit("TW_LIB is not the diagnostic build (tw_prof_read missing)")
     read(eng)
@@ -115,7 +117,14 @@ def main():
         d = read(eng)
         ms = float(eng.launch_ms().sum())
         pops = max(d["pop"], 1)
+        # the killThread sweep of this phase (the teardown's): its kernels' device time, part
+        # of kernel_ms, and what they retired -- those pops are in `events`, not in the counters
+        sw_ms = C.c_double(0.0)
+        if hasattr(eng.lib, "tw_sweep_ms"):
+            eng.lib.tw_sweep_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+            eng.lib.tw_sweep_ms(eng.ctx, C.byref(sw_ms))
         rec = {"phase": name, "events": st.events, "kernel_ms": round(ms, 3),
+               "sweep_ms": round(sw_ms.value, 3), "sweep": eng.sweep_stats(),
                "ev_per_s": st.events / max(ms, 1e-9) * 1e3,
                "kill_pop_share": round(d["kill_pop"] / pops, 4), "victim_pop_share": round(d["victim_pop"] / pops, 4),
                "cyc_per_kill_pop": round(d["cyc_kill_iter"] / max(d["kill_pop"], 1), 1),
