@@ -135,7 +135,11 @@ __device__ __forceinline__ bool load_killer(const Dev& c, const SweepTab& t, uin
     const bool two = (k.sw & SWB_TWO) != 0;
     const bool n2 = a0 < 2 || (two && a1 < 2), n3 = a0 >= 2 || (two && a1 >= 2);
     const uint4 z = make_uint4(0u, 0u, 0u, 0u);
-    const uint4 q2 = n2 ? *rec_q(c, e.z, r, 2) : z, q3 = n3 ? *rec_q(c, e.z, r, 3) : z;
+    // (not `n2 ? *rec_q(..) : z`: the conditional's uint4 temporary stays in
+    // memory, a scratch frame and a 16-byte scratch store per entry in both kernels)
+    uint4 q2 = z, q3 = z;
+    if (n2) q2 = *rec_q(c, e.z, r, 2);
+    if (n3) q3 = *rec_q(c, e.z, r, 3);
     k.ref0 = reg_of(q2, q3, a0);
     k.ref1 = two ? reg_of(q2, q3, a1) : 0ull;
     k.nref = two ? 2u : 1u;
@@ -228,30 +232,44 @@ __global__ void __launch_bounds__(64) tw_sweep_apply(Dev c, SweepTab t, int64_t 
             const uint4 e = *run_ent(c, j, pos, r);
             Killer k;
             if (!load_killer(c, t, r, e, T, k)) continue;  // (validated: cannot happen)
-            // the kill wake's pop: its resume term, then END (Lane::die_prep)
-            __hip_atomic_fetch_add((unsigned long long GAS*)(gp(c.hash) + (size_t)k.h.y * R + r),
-                                   (unsigned long long)term0(T, TW_KIND_RESUME | (k.h.x & 0xFFFFu)), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
+            // the kill wake's pop: END (Lane::die_prep); its resume term goes out below
             if (((k.h.x >> FL_SHIFT) & 0x3Fu) & F_OWNS) gp(c.bind_rel)[(size_t)k.h.y * R + r] = k.h.z;
             *rec_q(c, e.z, r, 0) = make_uint4(k.h.x | (F_STARTED << FL_SHIFT), k.h.y, 0xFFFFFFFFu, 0u);
             // the victim dies once: whoever takes its queued seq owns its pop
-            auto claim = [&](uint64_t ref) -> bool {
+            // (returns the victim's node, NONE for a ref that is stale or another killer's)
+            constexpr uint32_t NONE = 0xFFFFFFFFu;
+            auto claim = [&](uint64_t ref) -> uint32_t {
                 const uint32_t ts = (uint32_t)ref, tid = (uint32_t)(ref >> 32);
-                if (ts >= c.S) return false;
+                if (ts >= c.S) return NONE;
                 uint4 GAS* hp = rec_q(c, ts, r, 0);
                 const uint4 h = *hp;
-                if (h.z != tid) return false;  // stale, or claimed by another killer already
-                const uint32_t old = __hip_atomic_exchange((uint32_t GAS*)hp + 3, 0u, __ATOMIC_RELAXED,
-                                                           __HIP_MEMORY_SCOPE_AGENT);
-                if (old == 0) return false;
-                ((uint32_t GAS*)hp)[2] = 0xFFFFFFFFu;
-                __hip_atomic_fetch_add((unsigned long long GAS*)(gp(c.hash) + (size_t)h.y * R + r),
-                                       (unsigned long long)vterm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (h.z != tid) return NONE;  // stale, or claimed by another killer already
+                // its dead tid and the taken seq, w2 and w3, in one 8-byte swap (a
+                // killer that loses the race stores the same two words again)
+                const uint32_t old = (uint32_t)(__hip_atomic_exchange((unsigned long long GAS*)((uint32_t GAS*)hp + 2),
+                                                                      0x00000000FFFFFFFFull, __ATOMIC_RELAXED,
+                                                                      __HIP_MEMORY_SCOPE_AGENT) >> 32);
+                if (old == 0) return NONE;
                 if (((h.x >> FL_SHIFT) & 0x3Fu) & F_OWNS) gp(c.bind_rel)[(size_t)h.y * R + r] = tid;
-                return true;
+                return h.y;
             };
-            const bool c0 = claim(k.ref0);
-            const bool c1 = k.nref > 1 && claim(k.ref1);
+            const uint32_t n0 = claim(k.ref0);
+            const uint32_t n1 = k.nref > 1 ? claim(k.ref1) : NONE;
+            const bool c0 = n0 != NONE, c1 = n1 != NONE;
+            // the resume term and a ThreadKilled term per claimed victim: the
+            // terms of one node go out as one add (the hash is a sum mod 2^64)
+            unsigned long long kt = term0(T, TW_KIND_RESUME | (k.h.x & 0xFFFFu));
+            const bool m0 = c0 && n0 == k.h.y, m1 = c1 && n1 == k.h.y;
+            kt += (m0 ? vterm : 0ull) + (m1 ? vterm : 0ull);
+            __hip_atomic_fetch_add((unsigned long long GAS*)(gp(c.hash) + (size_t)k.h.y * R + r), kt, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+            const bool s0 = c0 && !m0, s1 = c1 && !m1, both = s0 && s1 && n0 == n1;
+            if (s0)
+                __hip_atomic_fetch_add((unsigned long long GAS*)(gp(c.hash) + (size_t)n0 * R + r),
+                                       both ? 2ull * vterm : vterm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (s1 && !both)
+                __hip_atomic_fetch_add((unsigned long long GAS*)(gp(c.hash) + (size_t)n1 * R + r), vterm, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
             const uint32_t nf = 1u + (c0 ? 1u : 0u) + (c1 ? 1u : 0u);
             nv += nf - 1u;
             // the freed slots go onto the free stack, behind what it held
