@@ -367,11 +367,27 @@ typedef struct tw_trace_rec {
 
 /* Record up to cap TRACE records per replica from the next tw_reset on
  * (0 = off, the default; the count beyond cap is still reported).  Call after
- * tw_load; allocates cap * n_replicas * 32 bytes of HBM. */
+ * tw_load or tw_lpb_load; allocates cap * n_replicas * 32 bytes of HBM.
+ *
+ * A batched node-partitioned context (tw_lpb_load) records too: a replica's
+ * nodes run as separate lanes, each record claims the replica's next index
+ * with one atomic (8 more bytes of HBM per replica), and the records are kept
+ * in claim order, which is no execution order (see tw_read_trace).  While
+ * tracing is on, such a context runs every due record on its node's chain: the
+ * data-parallel batch of tw_lpb_batch records nothing and stays off, so a
+ * traced run of a hotspot is slower than an untraced one.
+ * TW_ERR_INVALID for a node-partitioned context (tw_lp_load): its lanes are
+ * the nodes of one replica spread over contexts -- there is no replica
+ * execution order to record, and no one counter all of them could claim from. */
 int tw_set_trace(tw_ctx* ctx, uint32_t cap);
 
 /* A replica's trace records: copies min(cap, emitted, trace cap) records and
- * stores the number emitted (possibly more than were kept) in *n_emitted. */
+ * stores the number emitted (possibly more than were kept) in *n_emitted.
+ *
+ * A tw_lpb_load context returns the kept records sorted by (t, node, tag,
+ * val): a canonical order, not an execution order (the replica's nodes ran in
+ * parallel).  For a replica that emitted more than the trace cap, which cap of
+ * its records were kept is unspecified; *n_emitted is exact either way. */
 int tw_read_trace(tw_ctx* ctx, uint32_t replica, tw_trace_rec* out, size_t cap, uint64_t* n_emitted);
 
 /* ------------------------------------------------ measures joined on the GPU
@@ -382,7 +398,9 @@ int tw_read_trace(tw_ctx* ctx, uint32_t replica, tw_trace_rec* out, size_t cap, 
  * Only the csv / ODS rendering of single replicas stays on the host
  * (tw_read_trace).
  *
- * A replica's records are the kept ones, the first min(emitted, trace cap).
+ * A replica's records are the kept ones, the first min(emitted, trace cap)
+ * (tw_lpb_load: some min(emitted, trace cap) of them; the join groups by id and
+ * does not depend on their order).
  * A replica that emitted more than the cap is *truncated*: it adds 1 to
  * `truncated` and nothing else.  Within a replica the records whose tag is
  * tag_from or tag_to are grouped by `val` (the full int64: negative ids, 0 and
@@ -426,8 +444,11 @@ typedef struct tw_measure_out {
  * hashes and traces read afterwards are what they were) and may be called
  * repeatedly with different specs.  hist: n_bins counters or NULL; per_replica:
  * n entries in replica order or NULL (n = 0, or the context's replica count).
- * TW_ERR_STATE when nothing is loaded or tracing is off; TW_ERR_INVALID for an
- * LP / LPB context (as tw_set_trace: TRACE records exist in replica mode only),
+ * TW_ERR_STATE when nothing is loaded or tracing is off; TW_ERR_INVALID for a
+ * tw_lp_load context (as tw_set_trace: it keeps no TRACE records) and for a
+ * tw_lpb_load context with tracing off (TW_ERR_INVALID there, not TW_ERR_STATE:
+ * what such a context answered before it could trace; with tracing on it is
+ * measured like a replica context),
  * for a bad spec (tag_from == tag_to, n_bins == 0 or > TW_MEASURE_MAX_BINS,
  * bin_us < 1, reserved != 0), for another n, and when some non-truncated
  * replica holds more than TW_MEASURE_MAX_KEYS matching records -- decided on
@@ -606,7 +627,9 @@ int tw_lpb_windows(tw_ctx* ctx, uint64_t* windows, uint64_t* ticks);
  * effects are its own: registers, node-variable reads, links, traces, at most
  * one send followed by END; bench/Network's Ping handler) and no other event of
  * the node falls between their events.  Results are those of the sequential
- * loop either way; TW_LP_BATCH=0 at tw_lpb_load turns the batch off. */
+ * loop either way; TW_LP_BATCH=0 at tw_lpb_load turns the batch off, and so
+ * does tw_set_trace with a cap > 0 (the batch keeps no TRACE records: batched
+ * stays 0 and the due records run on their nodes' chains). */
 int tw_lpb_batch(tw_ctx* ctx, uint64_t* batched, uint64_t* due_records);
 
 /* ---- device-driven windows (no host round trip per window)

@@ -30,11 +30,13 @@
 //     bit-identical to the oracle's canonical mode.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <tuple>
 #include <vector>
 
 #include "../../include/timewarp.h"
@@ -153,7 +155,9 @@ void free_all(tw_shard* c) {
     for (void* p : c->allocs) (void)hipFree(p);
     c->allocs.clear();
     if (c->d.trace) (void)hipFree(c->d.trace);
+    if (c->d.trace_n) (void)hipFree(c->d.trace_n);
     c->d.trace = nullptr;
+    c->d.trace_n = nullptr;
     c->d.trace_cap = 0;
     if (c->ex_starts) (void)hipFree(c->ex_starts);
     if (c->ex_own) (void)hipFree(c->ex_own);
@@ -205,6 +209,23 @@ static void launch_run(tw_shard* c, hipStream_t st, int64_t t_end, uint64_t limi
         // batched device loop's per-replica windows (PRW)
         const bool gs = blocks > c->lp_grid, prw = c->d.rw && c->d.win;
         const dim3 g(gs ? c->lp_grid : blocks), b(WG * 64 / TPW);
+        // tw_set_trace on (batched LP only, sh_set_trace): the instantiations
+        // that keep TRACE records; the others compile Lane::trace_rec out
+        if (c->lpb && c->d.trace_cap) {
+            if (gs && prw)
+                hipLaunchKernelGGL((tw_run_kernel<LP, WG, NC, TPW, RUNS, true, true, false, true>), g, b, c->lds_bytes,
+                                   st, c->d, t_end, limit, budget);
+            else if (gs)
+                hipLaunchKernelGGL((tw_run_kernel<LP, WG, NC, TPW, RUNS, true, false, false, true>), g, b, c->lds_bytes,
+                                   st, c->d, t_end, limit, budget);
+            else if (prw)
+                hipLaunchKernelGGL((tw_run_kernel<LP, WG, NC, TPW, RUNS, false, true, false, true>), g, b, c->lds_bytes,
+                                   st, c->d, t_end, limit, budget);
+            else
+                hipLaunchKernelGGL((tw_run_kernel<LP, WG, NC, TPW, RUNS, false, false, false, true>), g, b,
+                                   c->lds_bytes, st, c->d, t_end, limit, budget);
+            return;
+        }
         if (gs && prw)
             hipLaunchKernelGGL((tw_run_kernel<LP, WG, NC, TPW, RUNS, true, true>), g, b, c->lds_bytes, st, c->d, t_end,
                                limit, budget);
@@ -512,6 +533,12 @@ static int load_common(tw_shard* c, const tw_scenario_desc* s, bool lp, uint32_t
         if (c->geo == 3) {
         } else if (lp) {
             HIPCHK(lds((const void*)tw_run_kernel<true, TW_WG_LP, TW_NEAR_LP>));
+            if (lpb) {  // the TRACE-recording instantiations (launch_run: every GS / PRW variant)
+                HIPCHK(lds((const void*)tw_run_kernel<true, TW_WG_LP, TW_NEAR_LP, 64, true, false, false, false, true>));
+                HIPCHK(lds((const void*)tw_run_kernel<true, TW_WG_LP, TW_NEAR_LP, 64, true, false, true, false, true>));
+                HIPCHK(lds((const void*)tw_run_kernel<true, TW_WG_LP, TW_NEAR_LP, 64, true, true, false, false, true>));
+                HIPCHK(lds((const void*)tw_run_kernel<true, TW_WG_LP, TW_NEAR_LP, 64, true, true, true, false, true>));
+            }
         } else if (c->geo == 1) {
             HIPCHK(lds((const void*)tw_run_kernel<false, TW_WG_SPARSE, TW_NEAR_SPARSE>));
         } else if (c->geo == 2) {
@@ -794,6 +821,7 @@ int sh_reset(tw_shard* c) {
         HIPCHK(hipMemsetAsync(d.hash_g, 0, 8ull * ((size_t)d.Ntot << d.rep_lg), st));
         HIPCHK(hipMemsetAsync(d.heavy_n, 0, 8, st));
         if (d.bat_ctr) HIPCHK(hipMemsetAsync(d.bat_ctr, 0, 16, st));
+        if (d.trace_n) HIPCHK(hipMemsetAsync(d.trace_n, 0, 8ull * c->n_rep, st));
         if (d.inlist) HIPCHK(hipMemsetAsync(d.inlist, 0, 4ull * R, st));
         HIPCHK(hipMemsetAsync(d.pend_min, 0xFF, 8, st));
         HIPCHK(hipMemsetAsync(d.out_n, 0, 4, st));
@@ -1359,7 +1387,9 @@ int sh_lp_clear_xmax(tw_shard* c) {
 // ran the batch's dry runs that the separate tw_lp_batch runs three workgroups
 // per CU wide)
 static int lp_window_start(tw_shard* c) {
-    const bool bat = c->heavy_ok && c->d.lpc_bat;
+    // (tracing on: tw_lp_batch runs handlers without Lane and would record
+    // nothing -- every due record stays on the lane's chain)
+    const bool bat = c->heavy_ok && c->d.lpc_bat && !c->d.trace_cap;
     if (c->heavy_ok) {
         hipLaunchKernelGGL(tw_lp_due, dim3(TW_DUE_GRID), dim3(256), 0, c->stream, c->dwin());
         HIPCHK(hipGetLastError());
@@ -1714,16 +1744,35 @@ int sh_device(tw_shard* c) { return c->device; }
 int sh_set_trace(tw_shard* c, uint32_t cap) {
     if (!c) return TW_ERR_INVALID;
     if (!c->loaded) return TW_ERR_STATE;
-    if (c->lp) return TW_ERR_INVALID;  // LP lanes are nodes: no replica execution order to record
+    // node-partitioned (tw_lp_load): LP lanes are nodes -- no replica execution
+    // order to record, and one counter for all lanes.  Batched LP records per
+    // replica, in claim order (Lane::trace_rec)
+    if (c->lp && !c->lpb) return TW_ERR_INVALID;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->d.trace) {
         HIPCHK(hipFree(c->d.trace));
         c->d.trace = nullptr;
     }
+    if (c->d.trace_n) {
+        HIPCHK(hipFree(c->d.trace_n));
+        c->d.trace_n = nullptr;
+    }
     c->d.trace_cap = 0;
     if (cap) {
-        HIPCHK(hipMalloc(&c->d.trace, (size_t)cap * c->d.R * 32));
+        // (batched LP: d.R counts lanes)
+        const size_t nrep = c->lpb ? c->n_rep : c->d.R;
+        HIPCHK(hipMalloc(&c->d.trace, (size_t)cap * nrep * 32));
+        if (c->lpb) {
+            if (hipMalloc(&c->d.trace_n, 8 * nrep) != hipSuccess) {
+                (void)hipGetLastError();
+                (void)hipFree(c->d.trace);
+                c->d.trace = nullptr;
+                return TW_ERR_OOM;
+            }
+            HIPCHK(hipMemsetAsync(c->d.trace_n, 0, 8 * nrep, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
         c->d.trace_cap = cap;
     }
     return TW_OK;
@@ -1733,10 +1782,15 @@ int sh_read_trace(tw_shard* c, uint32_t replica, tw_trace_rec* out, size_t cap, 
     if (!c || (cap && !out)) return TW_ERR_INVALID;
     if (!c->loaded) return TW_ERR_STATE;
     const Dev& d = c->d;
-    if (replica >= d.R) return TW_ERR_INVALID;
+    if (c->lp && !c->lpb) return TW_ERR_INVALID;
+    const size_t nrep = c->lpb ? c->n_rep : d.R;  // the records' replica stride (batched LP: d.R counts lanes)
+    if (replica >= nrep) return TW_ERR_INVALID;
     HIPCHK(hipSetDevice(c->device));
     uint64_t n = 0;
-    HIPCHK(hipMemcpyAsync(&n, d.scal + (size_t)SC_TRACE_N * d.R + replica, 8, hipMemcpyDeviceToHost, c->stream));
+    if (!c->lpb)
+        HIPCHK(hipMemcpyAsync(&n, d.scal + (size_t)SC_TRACE_N * d.R + replica, 8, hipMemcpyDeviceToHost, c->stream));
+    else if (d.trace_n)
+        HIPCHK(hipMemcpyAsync(&n, d.trace_n + replica, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (n_emitted) *n_emitted = n;
     size_t k = n < d.trace_cap ? (size_t)n : (size_t)d.trace_cap;
@@ -1744,9 +1798,19 @@ int sh_read_trace(tw_shard* c, uint32_t replica, tw_trace_rec* out, size_t cap, 
     if (k) {
         // records of one replica are strided by R: one 2D copy
         std::vector<uint4> buf(2 * k);
-        HIPCHK(hipMemcpy2DAsync(buf.data(), 32, d.trace + (size_t)replica * 2, (size_t)d.R * 32, 32, k,
+        HIPCHK(hipMemcpy2DAsync(buf.data(), 32, d.trace + (size_t)replica * 2, nrep * 32, 32, k,
                                 hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->lpb) {
+            // claim order says nothing: the canonical order (t, node, tag, val)
+            struct Q2 { uint4 a, b; };
+            Q2* q = reinterpret_cast<Q2*>(buf.data());
+            auto key = [](const Q2& x) {
+                return std::make_tuple((int64_t)(((uint64_t)x.a.y << 32) | x.a.x), x.a.z, x.a.w,
+                                       (int64_t)(((uint64_t)x.b.y << 32) | x.b.x));
+            };
+            std::sort(q, q + k, [&](const Q2& x, const Q2& y) { return key(x) < key(y); });
+        }
         for (size_t i = 0; i < k; ++i) {
             const uint4 a = buf[2 * i], b = buf[2 * i + 1];
             out[i].t = (int64_t)(((uint64_t)a.y << 32) | a.x);
@@ -1761,7 +1825,10 @@ int sh_read_trace(tw_shard* c, uint32_t replica, tw_trace_rec* out, size_t cap, 
 int sh_measure_state(tw_shard* c) {
     if (!c) return TW_ERR_INVALID;
     if (!c->loaded) return TW_ERR_STATE;
-    if (c->lp) return TW_ERR_INVALID;  // as sh_set_trace: TRACE records exist in replica mode only
+    // as sh_set_trace: node-partitioned contexts keep no TRACE records.  A
+    // batched LP context with tracing off keeps answering TW_ERR_INVALID too
+    // (what it answered before it could trace), not TW_ERR_STATE
+    if (c->lp && (!c->lpb || !c->d.trace || !c->d.trace_cap || !c->d.trace_n)) return TW_ERR_INVALID;
     if (!c->d.trace || !c->d.trace_cap) return TW_ERR_STATE;
     return TW_OK;
 }
@@ -1771,6 +1838,9 @@ int sh_measure(tw_shard* c, const tw_measure_spec* spec, tw_measure_out* total, 
     int rc = sh_measure_state(c);
     if (rc) return rc;
     const Dev& d = c->d;
+    if (c->lpb)  // (one count per replica in trace_n; d.R counts lanes)
+        return measure_run(c->device, c->stream, d.trace, d.trace_n, c->n_rep, d.trace_cap, spec, total, hist, per,
+                           kernel_ms);
     return measure_run(c->device, c->stream, d.trace, d.scal + (size_t)SC_TRACE_N * d.R, d.R, d.trace_cap, spec,
                        total, hist, per, kernel_ms);
 }

@@ -291,7 +291,9 @@ struct BoolC {
 
 // IP: fork children run in place (fork_in_place) -- the variant the host
 // launches under the tie orders where a forked child is always the next pop
-template <bool LP, int WG, int NC, bool RUNS = true, bool IP = false>
+// TR (LP only): TRACE records are kept (trace_rec) -- the variant the host
+// launches for a batched LP context while tw_set_trace is on
+template <bool LP, int WG, int NC, bool RUNS = true, bool IP = false, bool TR = false>
 struct Lane {
     // the replica kernels keep monotone far runs (LDS bookkeeping + HBM FIFOs)
     // unless built without them (the compact geometry: far events go to the
@@ -1449,9 +1451,29 @@ struct Lane {
         return false;
     }
 
-    // TRACE record (tw_set_trace): appended in this replica's execution order
+    // TRACE record (tw_set_trace): appended in this replica's execution order.
+    // LP lanes record in the TR variant only (the others are never launched
+    // with trace_cap != 0).  A replica's lanes are its nodes, spread over many
+    // waves, and the LP cold words have no room for a count (cw_count), so a
+    // record claims its index from the replica's counter in HBM, Dev::trace_n:
+    // one returning atomic per record; a wave's 64 lanes are 64 replicas of one
+    // node, so its atomics fall on 512 contiguous bytes.  The count goes on
+    // past the cap (tw_read_trace reports it); records are kept while the
+    // claimed index is below it, in claim order -- no execution order
     __device__ __forceinline__ void trace_rec(uint32_t node, int32_t tag, int64_t val) {
-        if constexpr (LP) return;  // (tw_set_trace refuses LP contexts: trace_cap is 0)
+        if constexpr (LP) {
+            if constexpr (TR) {
+                const uint32_t rh = rho();
+                const unsigned long long n = __hip_atomic_fetch_add(
+                    (unsigned long long GAS*)(gp(c.trace_n) + rh), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (n < c.trace_cap) {
+                    uint4 GAS* q = gp(c.trace) + ((((size_t)n << c.rep_lg) + rh) * 2);
+                    q[0] = make_uint4((uint32_t)now, (uint32_t)((uint64_t)now >> 32), node, (uint32_t)tag);
+                    q[1] = make_uint4((uint32_t)val, (uint32_t)((uint64_t)val >> 32), 0u, 0u);
+                }
+            }
+            return;
+        }
         const uint32_t n = cg(CW_TRN);
         cs(CW_TRN, n + 1);
         if (n < c.trace_cap) {
@@ -2467,12 +2489,15 @@ __host__ __device__ constexpr size_t fixed_lds_bytes() {
 // batches keep two workgroups per CU
 // LP lanes' prologue: the near spill's entries and the far heap's top loaded
 // together (round 6: C5 1,366 -> 1,341 ms, C4 flat)
-template <bool LP, int WG, int NC, int TPW = 64, bool RUNS = true, bool GS = false, bool PRW = false, bool IP = false>
+// TR: the LP kernel that keeps TRACE records (Lane::trace_rec)
+template <bool LP, int WG, int NC, int TPW = 64, bool RUNS = true, bool GS = false, bool PRW = false, bool IP = false,
+          bool TR = false>
 __global__ void __launch_bounds__(WG * 64 / TPW)
     __attribute__((amdgpu_waves_per_eu(LP ? TW_LP_WAVES : !RUNS ? 2 : (WG * 64 / TPW + 255) / 256,
                                        LP ? TW_LP_WAVES : 2)))
 tw_run_kernel(Dev c, int64_t t_end, uint64_t max_events, uint32_t budget) {
     constexpr bool HR = !LP && RUNS;
+    static_assert(LP || !TR, "TRACE-recording instantiations are LP kernels");
     // device-driven windows: the window, its work list and whether this is the
     // window's first tick (the only one that drains inboxes) come from the device
     bool fresh = true;
@@ -2609,7 +2634,7 @@ tw_run_kernel(Dev c, int64_t t_end, uint64_t max_events, uint32_t budget) {
                     break;  // (the next block of the work list)
             }
 
-            Lane<LP, WG, NC, RUNS, IP> L;
+            Lane<LP, WG, NC, RUNS, IP, TR> L;
             L.c = c;
             L.r = r;
             L.nk = s_k + li;
@@ -2997,7 +3022,7 @@ tw_run_kernel(Dev c, int64_t t_end, uint64_t max_events, uint32_t budget) {
                 const uint4 ix4 = *L.rqp(RQ_IDX);
         #pragma unroll
                 for (int j = 0; j < TW_RUNS; ++j) {
-                    sc[(SC_RH0 + j) * SR] = Lane<LP, WG, NC, RUNS, IP>::q_at(ix4, j);
+                    sc[(SC_RH0 + j) * SR] = Lane<LP, WG, NC, RUNS, IP, TR>::q_at(ix4, j);
                     sc[(SC_RC0 + j) * SR] = L.rqp(RQ_TAIL + j)->w;
                 }
             }

@@ -6,7 +6,10 @@
 // The TRACE records sit in HBM as [n][R][2] quads (tw_dev.hpp, written by
 // Lane::trace_rec and the wave kernel), the same layout under every replica
 // geometry, so one implementation serves dense / sparse / half / narrow /
-// compact / wave.  Two kernels:
+// compact / wave -- and a batched LP context (tw_lpb_load), whose traced event
+// kernel keeps the same [n][replicas][2] layout with one emitted count per
+// replica (Dev::trace_n); there n is a claim order, no execution order, which
+// the join (it groups by id) does not depend on.  Two kernels:
 //   tw_measure_count  one lane per replica walks n = 0..kept over the [n][R]
 //     layout (the lanes of a wave read neighbouring replicas: 32 B apart) and
 //     counts the records whose tag is tag_from or tag_to; a replica that
@@ -27,10 +30,12 @@
 // histogram 4096 x 4 B = 16 KiB, a few accumulators: ~50.1 KiB static, under
 // the 64 KiB a workgroup may hold; 3 workgroups per CU of the 160 KiB.
 //
-// Out of scope: TRACE records of LP / LPB contexts (tw_set_trace refuses
-// them; recording there touches the tuned LP event kernel -- this pass would
-// serve it unchanged), replicas with more than TW_MEASURE_MAX_KEYS matching
-// records (no global-memory sort path), a job-wide reduction over ranks.
+// Out of scope: TRACE records of node-partitioned contexts (tw_lp_load:
+// tw_set_trace refuses them -- one replica's nodes spread over contexts),
+// records of tw_lp_batch (a traced LPB run keeps its due records on the
+// lanes' chains instead), replicas with more than TW_MEASURE_MAX_KEYS
+// matching records (no global-memory sort path), a job-wide reduction over
+// ranks.
 #include <hip/hip_runtime.h>
 
 #include <climits>

@@ -39,14 +39,15 @@ TW_HIDDEN int sh_sweep_stats(tw_shard* c, uint64_t* killers, uint64_t* victims, 
 TW_HIDDEN int sh_set_trace(tw_shard* c, uint32_t cap);
 TW_HIDDEN int sh_read_trace(tw_shard* c, uint32_t replica, tw_trace_rec* out, size_t cap, uint64_t* n_emitted);
 // tw_measure on one shard: sh_measure_state is its state check alone
-// (TW_ERR_STATE nothing loaded / tracing off, TW_ERR_INVALID LP / LPB);
+// (TW_ERR_STATE nothing loaded / tracing off, TW_ERR_INVALID node-partitioned
+// contexts and batched LP contexts with tracing off);
 // sh_measure writes total, hist[n_bins] (or NULL), per[sh_replicas] (or NULL)
 // and the kernels' device time only on success
 TW_HIDDEN int sh_measure_state(tw_shard* c);
 TW_HIDDEN int sh_measure(tw_shard* c, const tw_measure_spec* spec, tw_measure_out* total, uint64_t* hist,
                          tw_measure_out* per, double* kernel_ms);
 // the measure pass itself (measure.hip) over a shard's trace buffer
-// ([cap][R][2] quads) and its per-replica emitted counts
+// ([cap][R][2] quads) and its per-replica emitted counts (R: replicas)
 TW_HIDDEN int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64_t* emitted, uint32_t R,
                           uint32_t cap, const tw_measure_spec* spec, tw_measure_out* total, uint64_t* hist,
                           tw_measure_out* per, double* kernel_ms);

@@ -185,7 +185,9 @@ struct Dev {
     // for the host-driven loop (tw_lp_window)
     int64_t* win;
     unsigned long long* prof;  // [P_COUNT] diagnostic build only
-    uint4* trace;        // [trace_cap][R][2] TRACE records (tw_set_trace), replica mode
+    uint4* trace;        // [trace_cap][replicas][2] TRACE records (tw_set_trace): replica mode (R replicas,
+                         // entry n = the replica's n-th TRACE) and batched LP (2^rep_lg replicas, entry n =
+                         // the n-th claim on trace_n: no execution order)
     uint32_t trace_cap;
     // handler stack beyond the record's two frames: [S][R][FXQ] quads (frames 2..)
     uint4* fx;
@@ -210,6 +212,9 @@ struct Dev {
     uint32_t* pq_free;
     uint4* pq_scr;
     uint32_t* pq_hdr;
+    // batched LP with tw_set_trace on: TRACE records emitted per replica, [2^rep_lg] (a replica
+    // context counts in SC_TRACE_N); every record claims its index here (Lane::trace_rec)
+    uint64_t* trace_n;
 };
 // index of scalar field f of lane / replica r
 __host__ __device__ __forceinline__ size_t sc_ix(const Dev& c, uint32_t f, size_t r) {

@@ -368,14 +368,21 @@ class Engine:
         return out
 
     def set_trace(self, cap: int) -> "Engine":
-        """Record up to `cap` TRACE records per replica from the next reset on."""
+        """Record up to `cap` TRACE records per replica from the next reset on
+        (0: off).  Replica geometries and "lpb" contexts record; a traced lpb
+        run keeps every due record on its node's chain (lpb_batch() reports
+        batched == 0), so it is slower than an untraced one.  A node-partitioned
+        context (tw_lp_load) answers ERR_INVALID."""
         _check(self.lib.tw_set_trace(self.ctx, int(cap)), "tw_set_trace")
         self._trace_cap = int(cap)
         return self
 
     def trace(self, replica: int, cap: int = 1 << 20):
         """(records, n_emitted): a replica's TRACE records in execution order
-        (TRACE_DTYPE), truncated at the trace capacity."""
+        (TRACE_DTYPE), truncated at the trace capacity.  An "lpb" context
+        returns them sorted by (t, node, tag, val) -- a canonical order, not an
+        execution order -- and, for a replica that emitted more than the
+        capacity, an unspecified `cap` of its records."""
         buf = np.zeros(cap, TRACE_DTYPE)
         n = C.c_uint64()
         _check(self.lib.tw_read_trace(self.ctx, int(replica), buf.ctypes.data, cap, C.byref(n)), "tw_read_trace")
@@ -388,7 +395,9 @@ class Engine:
         `total` a dict of tw_measure_out's fields, `hist` the n_bins uint64
         counters of bins [lo_us + i * bin_us, lo_us + (i + 1) * bin_us), and
         per_replica a MEASURE_DTYPE array in replica order (or None).  Needs
-        set_trace; reads only what the last run recorded."""
+        set_trace; reads only what the last run recorded.  Replica geometries
+        and "lpb" contexts alike (an lpb context with tracing off answers
+        ERR_INVALID, a replica context ERR_STATE)."""
         spec = TwMeasureSpec(tag_from=int(tag_from), tag_to=int(tag_to), n_bins=int(n_bins), reserved=0,
                              lo_us=int(lo_us), bin_us=int(bin_us))
         tot = TwMeasureOut()

@@ -5,7 +5,13 @@ tw_read_trace per replica plus measures_from_trace in the interpreter -- timed
 on a sample of replicas and scaled to the batch (an extrapolation).  The
 device's per-replica entries of the sample must equal measure_reference.
 
-usage: python tools/measure_probe.py [--senders 8] [--msgs 40] [--replicas 65536]
+--geometry lpb runs the batch in the batched logical-process mode (a power of
+two of at most 32768 replicas per GPU): its traced run keeps every due record on
+the node's chain (tw_lp_batch is off while tracing is on), and Engine.trace
+returns a replica's records in canonical order, so the host sample is compared
+as sorted tuples.
+
+usage: python tools/measure_probe.py [--senders 8] [--msgs 40] [--replicas 65536] [--geometry lpb]
                                      [--host-sample 256] [--out profiles/measure/probe.log]"""
 import argparse
 import os
@@ -26,6 +32,7 @@ ap.add_argument("--senders", type=int, default=8)
 ap.add_argument("--msgs", type=int, default=40)
 ap.add_argument("--replicas", type=int, default=65536)
 ap.add_argument("--host-sample", type=int, default=256)
+ap.add_argument("--geometry", default=None, help="Engine.load's geometry (default: the library's choice)")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "measure", "probe.log"))
 a = ap.parse_args()
 
@@ -42,11 +49,23 @@ def say(s):
 
 scn = scenarios.hotspot(n_senders=S, n_replicas=R, msg_num=M, drawer=draw_link_table)
 with Engine(0) as e:
-    e.load(scn).set_trace(cap).reset()
+    e.load(scn, geometry=a.geometry)
+    if a.geometry == "lpb":  # what tracing costs there: the same batch untraced, tw_lp_batch on
+        e.reset().run()      # (every timed run is a second one: the first loads code and captures the tick graph)
+        e.reset()
+        st = e.run()
+        batched, due = e.lpb_batch()
+        say(f"lpb untraced: event kernels {st.kernel_ms:.1f} ms, tw_run wall {st.wall_ms:.1f} ms; {due} due records, "
+            f"{batched} of them run by tw_lp_batch")
+    e.set_trace(cap).reset().run()
+    e.reset()
     st = e.run()
     say(f"hotspot {S} senders x {M} messages x {R} replicas, geometry {e.geometry()}: {st.events} events, "
         f"event kernels {st.kernel_ms:.1f} ms, tw_run wall {st.wall_ms:.1f} ms; {cap * R} trace records "
         f"({cap * R * 32 / 2**30:.2f} GiB)")
+    if a.geometry == "lpb":
+        batched, due = e.lpb_batch()
+        say(f"lpb: {due} due records, {batched} of them run by tw_lp_batch (off while tracing is on)")
     # device path: every replica, with the per-replica array
     for i in range(3):
         t0 = time.perf_counter()
@@ -69,7 +88,7 @@ with Engine(0) as e:
     t0 = time.perf_counter()
     for r in sample:
         rr, em = e.trace(int(r), cap=cap)
-        tup = trace_tuples(rr)
+        tup = sorted(trace_tuples(rr))  # (lpb: canonical order already; the join does not depend on order)
         ms = measures_from_trace(tup)
         lat = [m["PongReceived"] - m["PingSent"] for m in ms.values() if m and "PongReceived" in m and "PingSent" in m]
         recs.append(tup)
