@@ -504,6 +504,35 @@ int tw_set_sweep(tw_ctx* ctx, int on);
  * were refused (they took the sequential path).  Any pointer may be NULL. */
 int tw_sweep_stats(tw_ctx* ctx, uint64_t* killers, uint64_t* victims, uint64_t* refused_replicas);
 
+/* The send-free prefix (replica geometries DENSE, NARROW and HALF under
+ * TW_TIE_FIFO / TW_TIE_FORKFIRST, tracing off, a scenario without main_regs).
+ * Until a replica executes its first SEND it reads nothing of its own (the
+ * link table's column is a send's input), so every replica of the batch goes
+ * through the same states up to T0 - 1, where T0 is a load-time lower bound on
+ * the time of any thread's first SEND.  The first tw_run after a tw_reset
+ * that reaches T0 - 1 runs that stretch on one workgroup (the pilot), keeps
+ * one replica's state as a snapshot and stores it to every replica; later
+ * tw_reset / tw_run pairs of the loaded scenario store the cached snapshot
+ * instead of popping their way there.  Results, node hashes and statuses are
+ * the same either way; a pilot whose replica is not where the argument says
+ * (not running, at the event cap, a message counted) is refused and the run
+ * goes on as ever.  tw_load, tw_set_tie_mode and tw_set_counter_base drop the
+ * snapshot.  on != 0 enables it (the default after every tw_load), 0 disables
+ * it for later tw_run calls.  TW_ERR_STATE before tw_load. */
+enum tw_prefix_use {
+    TW_PREFIX_NOT_ELIGIBLE = 0, /* the run did not qualify (or max_events lies inside the prefix) */
+    TW_PREFIX_PILOTED = 1,      /* ran the pilot, took the snapshot and applied it  */
+    TW_PREFIX_APPLIED = 2,      /* applied the cached snapshot                      */
+    TW_PREFIX_REFUSED = 3       /* the pilot's check failed (now or for this key before) */
+};
+int tw_set_prefix(tw_ctx* ctx, int on);
+/* Of the context's first device: T0 of the loaded image (< 1: no prefix), the
+ * cached snapshot's events and bytes written per replica (0: no snapshot),
+ * what the last tw_run did (tw_prefix_use) and the device time of its apply.
+ * Any pointer may be NULL. */
+int tw_prefix_stats(tw_ctx* ctx, int64_t* t0_us, uint64_t* events_per_replica, uint64_t* bytes_per_replica,
+                    uint32_t* last_use, double* apply_ms);
+
 /* Testing hook: from the next tw_reset on, start every replica's insertion
  * counter at seq0 and its thread counter at tid0 (>= 1; main is tid 0), so the
  * TW_REP_ERR_COUNTER guard can be reached in a short run. */

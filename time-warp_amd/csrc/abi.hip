@@ -679,6 +679,21 @@ int tw_set_sweep(tw_ctx* c, int on) {
     return TW_OK;
 }
 
+int tw_set_prefix(tw_ctx* c, int on) {
+    if (!c) return TW_ERR_INVALID;
+    for (tw_shard* s : c->sh) {
+        int rc = sh_set_prefix(s, on);
+        if (rc) return rc;
+    }
+    return TW_OK;
+}
+
+int tw_prefix_stats(tw_ctx* c, int64_t* t0_us, uint64_t* events_per_replica, uint64_t* bytes_per_replica,
+                    uint32_t* last_use, double* apply_ms) {
+    if (!c || c->sh.empty()) return TW_ERR_INVALID;
+    return sh_prefix_stats(c->sh[0], t0_us, events_per_replica, bytes_per_replica, last_use, apply_ms);
+}
+
 int tw_sweep_stats(tw_ctx* c, uint64_t* killers, uint64_t* victims, uint64_t* refused_replicas) {
     if (!c) return TW_ERR_INVALID;
     uint64_t k = 0, v = 0, f = 0;

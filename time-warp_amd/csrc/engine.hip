@@ -44,6 +44,8 @@
 #include "shard.hpp"
 #include "sweep_classify.hpp"
 #include "sweep_dev.hpp"
+#include "prefix_classify.hpp"
+#include "prefix_dev.hpp"
 
 #include "engine_dev.hpp"
 
@@ -118,6 +120,22 @@ struct tw_shard {
     unsigned long long* h_sw = nullptr;  // pinned
     uint64_t sw_last[3] = {0, 0, 0};
     double sw_ms = 0.0;                  // device time of the last tw_run's sweeps
+    // the send-free prefix (prefix.hip): the image's bound T0
+    // (prefix_classify.hpp; < 1: none), whether a tw_reset came since the last
+    // tw_run, and the one cached snapshot with its key -- tie mode and counter
+    // bases -- or, px_ok false, the pilot's refusal for that key
+    bool px_on = true;
+    bool fresh = false;
+    int64_t px_t0 = 0;
+    bool px_have = false, px_ok = false;
+    uint32_t px_tie = 0, px_seq0 = 0, px_tid0 = 0;
+    tw::PrefixTab px{};
+    uint32_t px_max_es = 0;
+    uint64_t px_events = 0;              // events of a replica at the snapshot
+    size_t px_bytes = 0;                 // bytes the apply writes per replica
+    uint32_t px_last = TW_PREFIX_NOT_ELIGIBLE;  // what the last tw_run did
+    double px_ms = 0.0;                  // device time of the last tw_run's apply
+    hipEvent_t px_ev[2] = {nullptr, nullptr};
     Dev dwin() const {                // the descriptor the device loop's kernels get
         Dev x = d;
         x.win = win_buf;
@@ -151,9 +169,23 @@ int dalloc(tw_shard* c, T** p, size_t n) {
     return TW_OK;
 }
 
+// forget the cached prefix snapshot (tw_load, tw_set_tie_mode, tw_set_counter_base)
+void px_drop(tw_shard* c) {
+    if (c->px.rows) (void)hipFree((void*)c->px.rows);
+    if (c->px.snap) (void)hipFree(c->px.snap);
+    c->px = tw::PrefixTab{};
+    c->px_have = c->px_ok = false;
+    c->px_events = 0;
+    c->px_bytes = 0;
+    c->px_max_es = 0;
+}
+
 void free_all(tw_shard* c) {
     for (void* p : c->allocs) (void)hipFree(p);
     c->allocs.clear();
+    px_drop(c);
+    c->px_t0 = 0;
+    c->fresh = false;
     if (c->d.trace) (void)hipFree(c->d.trace);
     if (c->d.trace_n) (void)hipFree(c->d.trace_n);
     c->d.trace = nullptr;
@@ -201,8 +233,11 @@ static bool use_ip(const tw_shard* c) {
 }
 
 template <bool LP, int WG, int NC, int TPW = 64, bool RUNS = true>
-static void launch_run(tw_shard* c, hipStream_t st, int64_t t_end, uint64_t limit, uint32_t budget) {
-    const uint32_t blocks = (uint32_t)((c->d.R + WG - 1) / WG);
+static void launch_run(tw_shard* c, hipStream_t st, int64_t t_end, uint64_t limit, uint32_t budget,
+                       uint32_t grid = 0) {
+    // grid: workgroups to launch, 0 = one per WG replicas (the prefix pilot
+    // launches the first only; replica kernels, whose workgroups serve their own block)
+    const uint32_t blocks = (grid && !LP) ? grid : (uint32_t)((c->d.R + WG - 1) / WG);
     const bool ip = !LP && WG >= 64 && use_ip(c);
     if constexpr (LP) {
         // many lanes, few listed: the work list walked grid-stride (GS); the
@@ -283,6 +318,8 @@ void sh_destroy(tw_shard* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_all(c);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->px_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->h_active) (void)hipHostFree(c->h_active);
     if (c->h_st) (void)hipHostFree(c->h_st);
     if (c->h_win) (void)hipHostFree(c->h_win);
@@ -778,6 +815,12 @@ static int load_common(tw_shard* c, const tw_scenario_desc* s, bool lp, uint32_t
             (void)hipGetLastError();  // (a failed allocation is not an error of the load)
         }
     }
+    // the send-free prefix (prefix_classify.hpp): replica contexts only
+    c->px_on = true;
+    c->px_t0 = lp ? 0 : prefix_t0(s->insns, s->n_insns, s->consts, s->n_consts, s->main_pc);
+    // (an image that never sends ends inside its prefix: the pilot would run the
+    // first workgroup's replicas to the end, without sweeps, and be refused)
+    if (c->px_t0 == INT64_MAX) c->px_t0 = 0;
     d.insns = insns; d.consts = consts; d.lpc = lpc; d.out_off = out_off; d.link_dst = ldst; d.link_rev = lrev;
     d.link_table = ltab;
     c->main_pc = s->main_pc;
@@ -845,15 +888,133 @@ int sh_reset(tw_shard* c) {
                        (const int64_t*)c->main_regs, (const int64_t*)c->nv_init, (const uint32_t*)c->listen_init,
                        c->lp ? 1 : 0, c->seq0, c->tid0);
     HIPCHK(hipGetLastError());
+    c->fresh = true;
     return TW_OK;
 }
 
 
 static int lpb_run(tw_shard* c, tw_stats* out);
 
+// one launch of the context's event kernel to t_end (grid: launch_run)
+static int launch_event(tw_shard* c, hipStream_t st, int64_t t_end, uint64_t limit, uint32_t budget, uint32_t grid = 0) {
+    if (c->lp)
+        launch_run<true, TW_WG_LP, TW_NEAR_LP>(c, st, t_end, limit, budget);
+    else if (c->geo == 3)
+        HIPCHK(wave_launch(c->d, c->d_dev, st, t_end, limit, 1u << 16));
+    else if (c->geo == 1)
+        launch_run<false, TW_WG_SPARSE, TW_NEAR_SPARSE>(c, st, t_end, limit, budget, grid);
+    else if (c->geo == 2)
+        launch_run<false, TW_WG, TW_NEAR_CAP, TW_HALF_LANES>(c, st, t_end, limit, budget, grid);
+    else if (c->geo == 5)
+        launch_run<false, TW_NARROW, TW_NEAR_CAP, TW_NARROW>(c, st, t_end, limit, budget, grid);
+    else if (c->geo == 7)
+        launch_run<false, TW_WG, TW_NEAR_COMPACT, 64, false>(c, st, t_end, limit, budget, grid);
+    else
+        launch_run<false, TW_WG, TW_NEAR_CAP>(c, st, t_end, limit, budget, grid);
+    HIPCHK(hipGetLastError());
+    return TW_OK;
+}
+
+// The send-free prefix of a fresh run.  With a snapshot cached
+// for the context's tie mode and counter bases, its apply goes onto the stream
+// (between c->px_ev: the caller reads its time at its first sync).  Without
+// one, the first workgroup alone runs to T0 - 1 -- the pilot: the ordinary
+// run's first segment on a grid of one, no sweeps behind it --, replica 0 is
+// checked to have run as every replica must (still running, under the event
+// cap, no message counted, no send ordinal taken), its parked state becomes
+// the snapshot and is applied to every replica, the pilot's own included.  A
+// pilot that fails the check is remembered as "no prefix" for the key; its
+// replicas are simply ahead of the others and the run goes on as ever.
+// *applied: the apply is on the stream.
+static int run_prefix(tw_shard* c, uint64_t limit, uint32_t budget, uint32_t* launches, double* kms, bool* applied) {
+    const Dev& d = c->d;
+    hipStream_t st = c->stream;
+    *applied = false;
+    for (int i = 0; i < 2; ++i)
+        if (!c->px_ev[i]) HIPCHK(hipEventCreate(&c->px_ev[i]));
+    const bool hit = c->px_have && c->px_tie == d.tie_mode && c->px_seq0 == c->seq0 && c->px_tid0 == c->tid0;
+    if (hit && !c->px_ok) { c->px_last = TW_PREFIX_REFUSED; return TW_OK; }
+    if (hit && limit < c->px_events) return TW_OK;  // (the cap falls inside the prefix: the ordinary run)
+    if (!hit) {
+        HIPCHK(hipStreamSynchronize(st));
+        px_drop(c);
+        c->px_have = true;
+        c->px_tie = d.tie_mode; c->px_seq0 = c->seq0; c->px_tid0 = c->tid0;
+        c->px_last = TW_PREFIX_REFUSED;
+        const int per_check = 4;
+        while (c->ev_pool.size() < 2 * (size_t)per_check) {
+            hipEvent_t e;
+            HIPCHK(hipEventCreate(&e));
+            c->ev_pool.push_back(e);
+        }
+        bool parked = false;
+        for (int round = 0; round < (1 << 20) && !parked; ++round) {
+            for (int i = 0; i < per_check; ++i) {
+                HIPCHK(hipMemsetAsync(d.n_active, 0, 4, st));
+                HIPCHK(hipEventRecord(c->ev_pool[2 * i], st));
+                int rc = launch_event(c, st, c->px_t0 - 1, limit, budget, 1u);
+                if (rc) return rc;
+                HIPCHK(hipEventRecord(c->ev_pool[2 * i + 1], st));
+                ++*launches;
+            }
+            HIPCHK(hipMemcpyAsync(c->h_active, d.n_active, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            for (int i = 0; i < per_check; ++i) {
+                float ms = 0.f;
+                HIPCHK(hipEventElapsedTime(&ms, c->ev_pool[2 * i], c->ev_pool[2 * i + 1]));
+                c->launch_ms.push_back(ms);
+                *kms += ms;
+            }
+            parked = *c->h_active == 0;
+        }
+        if (!parked) return TW_OK;
+        // replica 0's scalar block; with D > 1 its send ordinals
+        uint64_t sc[SC_COUNT];
+        HIPCHK(hipMemcpy2DAsync(sc, 8, d.scal, 8ull * d.R, 8, SC_COUNT, hipMemcpyDeviceToHost, st));
+        std::vector<uint32_t> ord(d.D > 1 ? d.L : 0u);
+        if (!ord.empty())
+            HIPCHK(hipMemcpy2DAsync(ord.data(), 4, d.link_ord, 4ull * d.R, 4, ord.size(), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        bool ok = sc[SC_STATUS] == TW_REP_RUNNING && sc[SC_EVENTS] < limit && sc[SC_DELIVERED] == 0 &&
+                  sc[SC_DROPPED] == 0 && sc[SC_UNDELIV] == 0;
+        for (uint32_t o : ord) ok = ok && o == 0;
+        std::vector<tw::PrefixRow> rows;
+        size_t bytes = 0;
+        if (!ok || !prefix_directory(d, sc, TW_NEAR_CAP, rows, bytes)) return TW_OK;
+        void *drows = nullptr, *dsnap = nullptr;
+        if (hipMalloc(&drows, sizeof(tw::PrefixRow) * rows.size()) != hipSuccess ||
+            hipMalloc(&dsnap, bytes ? bytes : 1) != hipSuccess) {
+            (void)hipGetLastError();  // (no memory for the snapshot: no prefix, not an error of the run)
+            if (drows) (void)hipFree(drows);
+            return TW_OK;
+        }
+        c->px.rows = (const tw::PrefixRow*)drows;
+        c->px.snap = (uint8_t*)dsnap;
+        c->px.n_rows = (uint32_t)rows.size();
+        HIPCHK(hipMemcpy(drows, rows.data(), sizeof(tw::PrefixRow) * rows.size(), hipMemcpyHostToDevice));
+        uint32_t mx = 0;
+        for (const tw::PrefixRow& r : rows) mx = r.es > mx ? r.es : mx;
+        c->px_max_es = mx;
+        c->px_events = sc[SC_EVENTS];
+        c->px_bytes = bytes;
+        HIPCHK(prefix_take(c->px, st));
+        c->px_ok = true;
+    }
+    HIPCHK(hipEventRecord(c->px_ev[0], st));
+    HIPCHK(prefix_apply(c->px, d.R, c->px_max_es, st));
+    HIPCHK(hipEventRecord(c->px_ev[1], st));
+    c->px_last = hit ? TW_PREFIX_APPLIED : TW_PREFIX_PILOTED;
+    *applied = true;
+    return TW_OK;
+}
+
 int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
     if (!c) return TW_ERR_INVALID;
     if (!c->loaded) return TW_ERR_STATE;
+    const bool was_fresh = c->fresh;
+    c->fresh = false;
+    c->px_last = TW_PREFIX_NOT_ELIGIBLE;
+    c->px_ms = 0.0;
     if (c->lpb) {
         // the batched window loop runs every replica to quiescence
         if (t_end_us != INT64_MAX || max_events != UINT64_MAX) return TW_ERR_INVALID;
@@ -901,6 +1062,19 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
     uint32_t launches = 0;
     double kms = 0.0;
     bool quiet = false;
+    // the send-free prefix: a fresh replica run that reaches T0 - 1
+    // starts from the snapshot of that moment instead of popping its way there
+    bool px_pending = false;
+    if (was_fresh && c->px_on && !c->lp && (c->geo == 0 || c->geo == 2 || c->geo == 5) &&
+        (d.tie_mode == TW_TIE_FIFO || d.tie_mode == TW_TIE_FORKFIRST) && d.trace_cap == 0 && !c->main_regs &&
+        c->px_t0 >= 1 && t_end_us >= c->px_t0 - 1) {
+        int rc = run_prefix(c, limit, budget, &launches, &kms, &px_pending);
+        if (rc) return rc;
+        // (sweep times inside the prefix: the snapshot is past them)
+        if (px_pending)
+            for (uint32_t i = 0; i < c->sw_times.size(); ++i)
+                if (c->sw_times[i] <= c->px_t0 - 1) c->sw_done |= 1u << i;
+    }
     // killThread sweeps: the run is split at every sweep time T of
     // the image that lies within it.  While such a stop is ahead, the event
     // kernel runs to T - 1 (its "parked beyond t_end" path) and every launch is
@@ -938,21 +1112,10 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
             HIPCHK(hipMemsetAsync(d.n_active, 0, 4, st));
             if (c->lp) HIPCHK(hipMemsetAsync(d.next_t, 0xFF, 8, st));
             HIPCHK(hipEventRecord(c->ev_pool[2 * i], st));
-            if (c->lp)
-                launch_run<true, TW_WG_LP, TW_NEAR_LP>(c, st, te_seg, limit, budget);
-            else if (c->geo == 3)
-                HIPCHK(wave_launch(c->d, c->d_dev, st, te_seg, limit, 1u << 16));
-            else if (c->geo == 1)
-                launch_run<false, TW_WG_SPARSE, TW_NEAR_SPARSE>(c, st, te_seg, limit, budget);
-            else if (c->geo == 2)
-                launch_run<false, TW_WG, TW_NEAR_CAP, TW_HALF_LANES>(c, st, te_seg, limit, budget);
-            else if (c->geo == 5)
-                launch_run<false, TW_NARROW, TW_NEAR_CAP, TW_NARROW>(c, st, te_seg, limit, budget);
-            else if (c->geo == 7)
-                launch_run<false, TW_WG, TW_NEAR_COMPACT, 64, false>(c, st, te_seg, limit, budget);
-            else
-                launch_run<false, TW_WG, TW_NEAR_CAP>(c, st, te_seg, limit, budget);
-            HIPCHK(hipGetLastError());
+            {
+                int rc = launch_event(c, st, te_seg, limit, budget);
+                if (rc) return rc;
+            }
             HIPCHK(hipEventRecord(c->ev_pool[2 * i + 1], st));
             ++launches;
             if (to_sweep) {
@@ -964,6 +1127,15 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
         HIPCHK(hipMemcpyAsync(c->h_active, d.n_active, 4, hipMemcpyDeviceToHost, st));
         if (to_sweep) HIPCHK(hipMemcpyAsync(c->h_sw, c->sw.stats, 8 * SWS_COUNT, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
+        if (px_pending) {
+            // (the prefix apply in front of this round's first launch: device time of the step)
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, c->px_ev[0], c->px_ev[1]));
+            c->launch_ms.push_back(ms);
+            kms += ms;
+            c->px_ms = ms;
+            px_pending = false;
+        }
         for (int i = 0; i < per_check; ++i) {
             float ms = 0.f;
             HIPCHK(hipEventElapsedTime(&ms, c->ev_pool[2 * i], c->ev_pool[2 * i + 1]));
@@ -1125,6 +1297,9 @@ int sh_set_tie_mode(tw_shard* c, uint32_t mode) {
         }
     }
     c->d.tie_mode = mode;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    px_drop(c);
     return TW_OK;
 }
 
@@ -1132,6 +1307,31 @@ int sh_set_counter_base(tw_shard* c, uint32_t seq0, uint32_t tid0) {
     if (!c || tid0 == 0) return TW_ERR_INVALID;
     c->seq0 = seq0;
     c->tid0 = tid0;
+    if (c->px_have) {
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        px_drop(c);
+    }
+    return TW_OK;
+}
+
+// The send-free prefix of later tw_run calls (include/timewarp.h tw_set_prefix);
+// on after every tw_load.
+int sh_set_prefix(tw_shard* c, int on) {
+    if (!c) return TW_ERR_INVALID;
+    if (!c->loaded) return TW_ERR_STATE;
+    c->px_on = on != 0;
+    return TW_OK;
+}
+
+int sh_prefix_stats(tw_shard* c, int64_t* t0, uint64_t* events, uint64_t* bytes, uint32_t* last, double* ms) {
+    if (!c) return TW_ERR_INVALID;
+    if (!c->loaded) return TW_ERR_STATE;
+    if (t0) *t0 = c->px_t0;
+    if (events) *events = c->px_ok ? c->px_events : 0;
+    if (bytes) *bytes = c->px_ok ? c->px_bytes : 0;
+    if (last) *last = c->px_last;
+    if (ms) *ms = c->px_ms;
     return TW_OK;
 }
 

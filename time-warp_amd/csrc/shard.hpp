@@ -36,6 +36,11 @@ TW_HIDDEN int sh_set_tie_mode(tw_shard* c, uint32_t mode);
 // the sweep kernels' device time
 TW_HIDDEN int sh_set_sweep(tw_shard* c, int on);
 TW_HIDDEN int sh_sweep_stats(tw_shard* c, uint64_t* killers, uint64_t* victims, uint64_t* refused, double* ms);
+// the send-free prefix (prefix.hip): the switch; the image's T0, the cached
+// snapshot's events and bytes per replica (0: none), what the last sh_run did
+// (TW_PREFIX_*) and its apply's device time
+TW_HIDDEN int sh_set_prefix(tw_shard* c, int on);
+TW_HIDDEN int sh_prefix_stats(tw_shard* c, int64_t* t0, uint64_t* events, uint64_t* bytes, uint32_t* last, double* ms);
 TW_HIDDEN int sh_set_trace(tw_shard* c, uint32_t cap);
 TW_HIDDEN int sh_read_trace(tw_shard* c, uint32_t replica, tw_trace_rec* out, size_t cap, uint64_t* n_emitted);
 // tw_measure on one shard: sh_measure_state is its state check alone

@@ -32,10 +32,10 @@ __device__ __forceinline__ uint32_t GAS* acc_at(const SweepTab& t, const Dev& c,
     return gp(t.acc) + (size_t)w * c.R + r;
 }
 __device__ __forceinline__ uint4 GAS* run_ent(const Dev& c, uint32_t j, uint32_t pos, uint32_t r) {
-    return gp(c.runs) + ((size_t)j * c.Cr + pos) * c.R + r;
+    return gp(c.runs) + run_row(c, j, pos) + r;
 }
 __device__ __forceinline__ uint4 GAS* rec_q(const Dev& c, uint32_t slot, uint32_t r, uint32_t q) {
-    return gp(c.slots) + (size_t)q * c.RQ + (size_t)slot * c.R + r;
+    return gp(c.slots) + rec_row(c, slot, q) + r;
 }
 __device__ __forceinline__ uint32_t seq_limit(const Dev& c) {
     return c.tie_mode == TW_TIE_FORKFIRST ? 0x7FFFFFFFu : 0xFFFFFFFFu;

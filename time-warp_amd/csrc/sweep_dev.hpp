@@ -28,6 +28,16 @@ struct SweepTab {
     uint32_t near_cap;          // entries of the near spill per replica
 };
 
+// The parked layout the event kernel's epilogue leaves (shared with prefix.hip):
+// element index of replica 0's entry `pos` of far run j, and of quad q of the
+// thread record in `slot`; replica r's lies r elements on.
+__host__ __device__ __forceinline__ size_t run_row(const Dev& c, uint32_t j, uint32_t pos) {
+    return ((size_t)j * c.Cr + pos) * c.R;
+}
+__host__ __device__ __forceinline__ size_t rec_row(const Dev& c, uint32_t slot, uint32_t q) {
+    return (size_t)q * c.RQ + (size_t)slot * c.R;
+}
+
 size_t sweep_acc_words(uint32_t R);
 // The sweep at time T of the run's stop number `expect`, on stream st, behind an
 // event-kernel launch to T - 1: it runs if that launch left every replica

@@ -31,7 +31,8 @@ EXPORTS = ["tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_ru
            "tw_set_trace", "tw_read_trace", "tw_tie_audit", "tw_set_counter_base", "tw_geometry",
            "tw_set_stream", "tw_lp_exchange_setup", "tw_lp_loop_begin", "tw_lp_tick", "tw_lp_tick_import",
            "tw_lp_tick_end", "tw_lp_progress", "tw_lp_run_windows", "tw_lpb_load", "tw_lpb_windows",
-           "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms", "tw_set_sweep", "tw_sweep_stats"]
+           "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms", "tw_set_sweep", "tw_sweep_stats",
+           "tw_set_prefix", "tw_prefix_stats"]
 GEOMETRIES = ("dense", "sparse", "half", "wave", "lp", "narrow", "lpb", "compact")  # TW_GEO_* order
 
 # tw_trace_rec (include/timewarp.h)
@@ -112,13 +113,16 @@ def load_library(path: Optional[str] = None):
     lib.tw_measure_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.tw_set_sweep.argtypes = [C.c_void_p, C.c_int]
     lib.tw_sweep_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
+    lib.tw_set_prefix.argtypes = [C.c_void_p, C.c_int]
+    lib.tw_prefix_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
     for name in ("tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_run", "tw_set_tie_mode", "tw_load", "tw_reset", "tw_run", "tw_read_results", "tw_read_hashes", "tw_read_final",
                  "tw_last_launch_ms", "tw_lp_load", "tw_lp_window", "tw_lp_take_outbox", "tw_lp_inject",
                  "tw_lp_results", "tw_set_trace", "tw_read_trace", "tw_tie_audit", "tw_set_counter_base",
                  "tw_geometry", "tw_set_stream", "tw_lp_exchange_setup", "tw_lp_loop_begin", "tw_lp_tick",
                  "tw_lp_tick_import", "tw_lp_tick_end", "tw_lp_progress", "tw_lp_run_windows", "tw_lpb_load",
                  "tw_lpb_windows", "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms", "tw_set_sweep",
-                 "tw_sweep_stats"):
+                 "tw_sweep_stats", "tw_set_prefix", "tw_prefix_stats"):
         getattr(lib, name).restype = C.c_int
     if path is None:
         _lib = lib
@@ -350,6 +354,27 @@ class Engine:
         k, v, f = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         _check(self.lib.tw_sweep_stats(self.ctx, C.byref(k), C.byref(v), C.byref(f)), "tw_sweep_stats")
         return {"killers": int(k.value), "victims": int(v.value), "refused_replicas": int(f.value)}
+
+    PREFIX_USE = ("not_eligible", "piloted", "applied", "refused")  # tw_prefix_use
+
+    def set_prefix(self, on: bool) -> "Engine":
+        """The send-free prefix of later runs (tw_set_prefix): on after every
+        load.  A fresh run that reaches T0 - 1 (T0: a lower bound on the time
+        of the image's first send) starts from a snapshot of that moment,
+        computed once per loaded scenario, tie mode and counter base, instead
+        of popping its way there.  Results are the same either way."""
+        _check(self.lib.tw_set_prefix(self.ctx, 1 if on else 0), "tw_set_prefix")
+        return self
+
+    def prefix_stats(self) -> dict:
+        """T0 of the loaded image, the cached snapshot's events and bytes per
+        replica (0: none), what the last run did (PREFIX_USE) and its apply's
+        device time in ms (tw_prefix_stats)."""
+        t0, ev, by, use, ms = C.c_int64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0), C.c_double(0.0)
+        _check(self.lib.tw_prefix_stats(self.ctx, C.byref(t0), C.byref(ev), C.byref(by), C.byref(use), C.byref(ms)),
+               "tw_prefix_stats")
+        return {"t0": int(t0.value), "events": int(ev.value), "bytes": int(by.value),
+                "last": self.PREFIX_USE[use.value], "apply_ms": float(ms.value)}
 
     def set_counter_base(self, seq0: int, tid0: int = 1) -> "Engine":
         """Testing hook: start the 32-bit insertion / thread counters at these
