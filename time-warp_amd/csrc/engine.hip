@@ -37,11 +37,13 @@
 #include <cstring>
 #include <new>
 #include <tuple>
+#include <utility>
 #include <vector>
 
 #include "../../include/timewarp.h"
 #include "tw_dev.hpp"
 #include "shard.hpp"
+#include "run_state.hpp"
 #include "sweep_classify.hpp"
 #include "sweep_dev.hpp"
 #include "prefix_classify.hpp"
@@ -67,7 +69,7 @@ struct tw_shard {
     int64_t* nv_init = nullptr;
     uint32_t* listen_init = nullptr;
     size_t lds_bytes = 0;
-    int geo = 0;  // 0: dense (TW_WG, TW_NEAR_CAP); 1: sparse (TW_WG_SPARSE, TW_NEAR_SPARSE); 2: half (TW_WG, TW_NEAR_CAP, TW_HALF_LANES lanes per wave)
+    int geo = TW_GEO_DENSE;  // a replica geometry's TW_GEO_* (LP contexts: dense, unused; with_geo)
     // LP mode
     bool lp = false;
     bool lpb = false;               // batched LP (tw_lpb_load): R = nodes x replicas
@@ -79,8 +81,7 @@ struct tw_shard {
     uint4* foreign = nullptr;      // [out_cap][2]
     uint32_t* n_foreign = nullptr;
     uint4* staging = nullptr;      // inject staging [out_cap][2]
-    std::vector<double> launch_ms;
-    std::vector<hipEvent_t> ev_pool;
+    LaunchTimes times;              // of the last tw_run (tw_last_launch_ms, tw_stats.kernel_ms)
     std::vector<uint32_t> tie_flags;  // tw_tie_audit, per replica
     Dev* d_dev = nullptr;             // device copy of d (the wave kernel reads it through the scalar cache)
     uint32_t seq0 = 0, tid0 = 1;      // tw_set_counter_base
@@ -109,33 +110,8 @@ struct tw_shard {
     // for tests: a small budget makes windows take several ticks)
     uint32_t lp_budget = 1u << 14;
     uint32_t lp_grid = TW_LP_GRID;  // LP launches above this many workgroups walk the list (TW_LP_GRID env)
-    // killThread sweeps (sweep.hip): the classifier's tables and the
-    // sweep kernels' scratch (sw.stub null: no kill stub in the image, or no
-    // memory for the scratch), the image's sweep times, which of them were swept
-    // since the last tw_reset, and the last tw_run's counts
-    bool sweep_on = true;
-    tw::SweepTab sw{};
-    std::vector<int64_t> sw_times;
-    uint32_t sw_done = 0;
-    unsigned long long* h_sw = nullptr;  // pinned
-    uint64_t sw_last[3] = {0, 0, 0};
-    double sw_ms = 0.0;                  // device time of the last tw_run's sweeps
-    // the send-free prefix (prefix.hip): the image's bound T0
-    // (prefix_classify.hpp; < 1: none), whether a tw_reset came since the last
-    // tw_run, and the one cached snapshot with its key -- tie mode and counter
-    // bases -- or, px_ok false, the pilot's refusal for that key
-    bool px_on = true;
-    bool fresh = false;
-    int64_t px_t0 = 0;
-    bool px_have = false, px_ok = false;
-    uint32_t px_tie = 0, px_seq0 = 0, px_tid0 = 0;
-    tw::PrefixTab px{};
-    uint32_t px_max_es = 0;
-    uint64_t px_events = 0;              // events of a replica at the snapshot
-    size_t px_bytes = 0;                 // bytes the apply writes per replica
-    uint32_t px_last = TW_PREFIX_NOT_ELIGIBLE;  // what the last tw_run did
-    double px_ms = 0.0;                  // device time of the last tw_run's apply
-    hipEvent_t px_ev[2] = {nullptr, nullptr};
+    Sweep sw;
+    Prefix px;
     Dev dwin() const {                // the descriptor the device loop's kernels get
         Dev x = d;
         x.win = win_buf;
@@ -144,20 +120,6 @@ struct tw_shard {
 };
 
 namespace {
-
-int hip_fail(hipError_t e) {
-    (void)e;
-    return TW_ERR_HIP;
-}
-
-#define HIPCHK(x)                                     \
-    do {                                              \
-        hipError_t _e = (x);                          \
-        if (_e != hipSuccess) {                       \
-            fprintf(stderr, "timewarp: %s failed: %s\n", #x, hipGetErrorString(_e)); \
-            return _e == hipErrorOutOfMemory ? TW_ERR_OOM : hip_fail(_e); \
-        }                                             \
-    } while (0)
 
 template <class T>
 int dalloc(tw_shard* c, T** p, size_t n) {
@@ -169,23 +131,11 @@ int dalloc(tw_shard* c, T** p, size_t n) {
     return TW_OK;
 }
 
-// forget the cached prefix snapshot (tw_load, tw_set_tie_mode, tw_set_counter_base)
-void px_drop(tw_shard* c) {
-    if (c->px.rows) (void)hipFree((void*)c->px.rows);
-    if (c->px.snap) (void)hipFree(c->px.snap);
-    c->px = tw::PrefixTab{};
-    c->px_have = c->px_ok = false;
-    c->px_events = 0;
-    c->px_bytes = 0;
-    c->px_max_es = 0;
-}
-
 void free_all(tw_shard* c) {
     for (void* p : c->allocs) (void)hipFree(p);
     c->allocs.clear();
-    px_drop(c);
-    c->px_t0 = 0;
-    c->fresh = false;
+    c->px.unload();
+    c->sw.unload();
     if (c->d.trace) (void)hipFree(c->d.trace);
     if (c->d.trace_n) (void)hipFree(c->d.trace_n);
     c->d.trace = nullptr;
@@ -212,78 +162,114 @@ void free_all(tw_shard* c) {
     if (c->tick_graph) (void)hipGraphExecDestroy(c->tick_graph);
     c->tick_graph = nullptr;
     c->tick_gkey.clear();
-    c->sw = tw::SweepTab{};
-    c->sw_times.clear();
-    c->sw_done = 0;
     c->loaded = false;
 }
 
 }  // namespace
 
-// The fork-in-place variant (Lane::fork_in_place) of a replica geometry: under
-// the tie orders where a forked child is always the next pop (FORKFIRST,
-// LIFO), and for the compact geometry in every order.  Measured (round 4):
+// ============================================================ kernel geometries
+// One description per geometry of tw_run_kernel: its template arguments, whether
+// it has the fork-in-place variant (IP; sparse: compiled out, LP: its own inline
+// paths) and its near-spill entries per lane.  Everything the host knows about a
+// geometry is derived from here.  The wave geometry (wave.hip: wave_launch, no
+// LDS, wave_spill_entries) is the one special case: a branch where it matters.
+using RunKernel = void (*)(Dev, int64_t, uint64_t, uint32_t);
+template <bool LP_, int WG_, int NC_, int TPW_, bool RUNS_, bool IP_, int SPILL_>
+struct Geo {
+    static constexpr bool LP = LP_, RUNS = RUNS_, IP = IP_;
+    static constexpr int WG = WG_, NC = NC_, TPW = TPW_, SPILL = SPILL_;
+    static constexpr bool FAR_RUNS = !LP_ && RUNS_;  // (LP lanes and compact replicas: the HBM heap only)
+    static constexpr size_t LDS = fixed_lds_bytes<WG_, NC_, LP_, RUNS_>();
+    template <bool GS, bool PRW, bool FIP, bool TR>
+    static RunKernel kernel() {
+        return tw_run_kernel<LP_, WG_, NC_, TPW_, RUNS_, GS, PRW, FIP, TR>;
+    }
+};
+using GeoDense = Geo<false, TW_WG, TW_NEAR_CAP, 64, true, true, TW_NEAR_CAP>;
+using GeoSparse = Geo<false, TW_WG_SPARSE, TW_NEAR_SPARSE, 64, true, false, TW_NEAR_SPARSE>;
+using GeoHalf = Geo<false, TW_WG, TW_NEAR_CAP, TW_HALF_LANES, true, true, TW_NEAR_CAP>;
+using GeoNarrow = Geo<false, TW_NARROW, TW_NEAR_CAP, TW_NARROW, true, (TW_NARROW >= 64), TW_NEAR_CAP>;
+using GeoCompact = Geo<false, TW_WG, TW_NEAR_COMPACT, 64, false, true, TW_NEAR_CAP>;
+using GeoLP = Geo<true, TW_WG_LP, TW_NEAR_LP, 64, true, false, TW_NEAR_LP>;
+
+// f(description) of the context's geometry (not the wave geometry's)
+template <class F>
+static auto with_geo(const tw_shard* c, F&& f) {
+    if (c->lp) return f(GeoLP{});
+    switch (c->geo) {
+    case TW_GEO_SPARSE: return f(GeoSparse{});
+    case TW_GEO_HALF: return f(GeoHalf{});
+    case TW_GEO_NARROW: return f(GeoNarrow{});
+    case TW_GEO_COMPACT: return f(GeoCompact{});
+    default: return f(GeoDense{});
+    }
+}
+
+// The replica geometries the killThread sweeps and the send-free prefix serve:
+// far runs, and the dense near layout (TW_NEAR_CAP entries per lane) that
+// sweep.hip and prefix.hip read.  Both also need a tie order in which a parked
+// replica's equal-time entries pop in insertion order: ordered_ties.
+static bool far_run_geo(const tw_shard* c) {
+    return c->geo != TW_GEO_WAVE && with_geo(c, [](auto g) { return g.FAR_RUNS && g.NC == TW_NEAR_CAP; });
+}
+static bool ordered_ties(const tw_shard* c) {
+    return c->d.tie_mode == TW_TIE_FIFO || c->d.tie_mode == TW_TIE_FORKFIRST;
+}
+
+// The instantiations of tw_run_kernel for geometry G, each with the variant it
+// is: what load_common registers and what launch_run picks from.
+//   LP: the work list walked grid-stride (gs: many lanes, few listed), the
+//   batched device loop's per-replica windows (prw), TRACE records kept (tr:
+//   tw_set_trace on, batched LP only; the others compile Lane::trace_rec out);
+//   replicas: the fork-in-place variant (ip: Lane::fork_in_place).
+struct Variant {
+    bool gs, prw, ip, tr;
+    bool operator==(const Variant& o) const { return gs == o.gs && prw == o.prw && ip == o.ip && tr == o.tr; }
+};
+template <class G, class F>
+static void each_kernel(F&& f) {  // f(RunKernel, Variant)
+    constexpr bool T = true, N = false;
+    f(G::template kernel<N, N, N, N>(), Variant{N, N, N, N});
+    if constexpr (G::IP) f(G::template kernel<N, N, T, N>(), Variant{N, N, T, N});
+    if constexpr (G::LP) {
+        f(G::template kernel<T, N, N, N>(), Variant{T, N, N, N});
+        f(G::template kernel<N, T, N, N>(), Variant{N, T, N, N});
+        f(G::template kernel<T, T, N, N>(), Variant{T, T, N, N});
+        f(G::template kernel<N, N, N, T>(), Variant{N, N, N, T});
+        f(G::template kernel<T, N, N, T>(), Variant{T, N, N, T});
+        f(G::template kernel<N, T, N, T>(), Variant{N, T, N, T});
+        f(G::template kernel<T, T, N, T>(), Variant{T, T, N, T});
+    }
+}
+
+// The fork-in-place variant of a replica geometry that has one: under the tie
+// orders where a forked child is always the next pop (FORKFIRST, LIFO), and
+// for the compact geometry in every order.  Measured (round 4):
 // C3 dense FIFO 17.8 G events/s without it, 16.3 G with it (the child is
 // rarely next under FIFO and the code costs registers), FORKFIRST 19.4 G;
 // C2 compact FIFO 39.7 G without, 43.2-44.0 G with (ping-pong forks into an
 // empty queue: the child is next under FIFO too)
+template <class G>
 static bool use_ip(const tw_shard* c) {
-    if (c->lp || c->geo == 1) return false;  // (LP: its own inline paths; sparse: compiled out)
-    return c->d.tie_mode == TW_TIE_FORKFIRST || c->d.tie_mode == TW_TIE_LIFO || c->geo == 7;
+    return G::IP &&
+           (c->d.tie_mode == TW_TIE_FORKFIRST || c->d.tie_mode == TW_TIE_LIFO || c->geo == TW_GEO_COMPACT);
 }
 
-template <bool LP, int WG, int NC, int TPW = 64, bool RUNS = true>
+template <class G>
 static void launch_run(tw_shard* c, hipStream_t st, int64_t t_end, uint64_t limit, uint32_t budget,
                        uint32_t grid = 0) {
     // grid: workgroups to launch, 0 = one per WG replicas (the prefix pilot
     // launches the first only; replica kernels, whose workgroups serve their own block)
-    const uint32_t blocks = (grid && !LP) ? grid : (uint32_t)((c->d.R + WG - 1) / WG);
-    const bool ip = !LP && WG >= 64 && use_ip(c);
-    if constexpr (LP) {
-        // many lanes, few listed: the work list walked grid-stride (GS); the
-        // batched device loop's per-replica windows (PRW)
-        const bool gs = blocks > c->lp_grid, prw = c->d.rw && c->d.win;
-        const dim3 g(gs ? c->lp_grid : blocks), b(WG * 64 / TPW);
-        // tw_set_trace on (batched LP only, sh_set_trace): the instantiations
-        // that keep TRACE records; the others compile Lane::trace_rec out
-        if (c->lpb && c->d.trace_cap) {
-            if (gs && prw)
-                hipLaunchKernelGGL((tw_run_kernel<LP, WG, NC, TPW, RUNS, true, true, false, true>), g, b, c->lds_bytes,
-                                   st, c->d, t_end, limit, budget);
-            else if (gs)
-                hipLaunchKernelGGL((tw_run_kernel<LP, WG, NC, TPW, RUNS, true, false, false, true>), g, b, c->lds_bytes,
-                                   st, c->d, t_end, limit, budget);
-            else if (prw)
-                hipLaunchKernelGGL((tw_run_kernel<LP, WG, NC, TPW, RUNS, false, true, false, true>), g, b, c->lds_bytes,
-                                   st, c->d, t_end, limit, budget);
-            else
-                hipLaunchKernelGGL((tw_run_kernel<LP, WG, NC, TPW, RUNS, false, false, false, true>), g, b,
-                                   c->lds_bytes, st, c->d, t_end, limit, budget);
-            return;
-        }
-        if (gs && prw)
-            hipLaunchKernelGGL((tw_run_kernel<LP, WG, NC, TPW, RUNS, true, true>), g, b, c->lds_bytes, st, c->d, t_end,
-                               limit, budget);
-        else if (gs)
-            hipLaunchKernelGGL((tw_run_kernel<LP, WG, NC, TPW, RUNS, true, false>), g, b, c->lds_bytes, st, c->d, t_end,
-                               limit, budget);
-        else if (prw)
-            hipLaunchKernelGGL((tw_run_kernel<LP, WG, NC, TPW, RUNS, false, true>), g, b, c->lds_bytes, st, c->d, t_end,
-                               limit, budget);
-        else
-            hipLaunchKernelGGL((tw_run_kernel<LP, WG, NC, TPW, RUNS>), g, b, c->lds_bytes, st, c->d, t_end, limit,
-                               budget);
-    } else {
-        if constexpr (WG >= 64) {
-            if (ip) {
-                hipLaunchKernelGGL((tw_run_kernel<LP, WG, NC, TPW, RUNS, false, false, true>), dim3(blocks),
-                                   dim3(WG * 64 / TPW), c->lds_bytes, st, c->d, t_end, limit, budget);
-                return;
-            }
-        }
-        hipLaunchKernelGGL((tw_run_kernel<LP, WG, NC, TPW, RUNS>), dim3(blocks), dim3(WG * 64 / TPW), c->lds_bytes, st,
-                           c->d, t_end, limit, budget);
+    uint32_t blocks = (grid && !G::LP) ? grid : (uint32_t)((c->d.R + G::WG - 1) / G::WG);
+    Variant v{false, false, use_ip<G>(c), false};
+    if constexpr (G::LP) {
+        v = Variant{blocks > c->lp_grid, c->d.rw && c->d.win, false, c->lpb && c->d.trace_cap != 0};
+        if (v.gs) blocks = c->lp_grid;
     }
+    each_kernel<G>([&](RunKernel k, Variant kv) {
+        if (kv == v)
+            hipLaunchKernelGGL(k, dim3(blocks), dim3(G::WG * 64 / G::TPW), c->lds_bytes, st, c->d, t_end, limit, budget);
+    });
 }
 
 namespace tw {
@@ -317,13 +303,11 @@ void sh_destroy(tw_shard* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_all(c);
-    for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->px_ev)
-        if (e) (void)hipEventDestroy(e);
+    c->times.destroy();
     if (c->h_active) (void)hipHostFree(c->h_active);
     if (c->h_st) (void)hipHostFree(c->h_st);
     if (c->h_win) (void)hipHostFree(c->h_win);
-    if (c->h_sw) (void)hipHostFree(c->h_sw);
+    if (c->sw.h) (void)hipHostFree(c->sw.h);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -543,54 +527,31 @@ static int load_common(tw_shard* c, const tw_scenario_desc* s, bool lp, uint32_t
         // dense batches of a scenario without far runs (run_capacity 0, e.g.
         // C2's ping-pong: every event within the near horizon) take the
         // compact geometry: two waves per SIMD
-        int geo = lp ? 0 : R <= 4096 ? 3 : R < 65536 ? 5 : (s->run_capacity == 0 ? 7 : 0);
-        if (g && !strcmp(g, "dense")) geo = 0;
-        if (g && !strcmp(g, "compact")) geo = 7;
-        if (g && !strcmp(g, "sparse")) geo = 1;
-        if (g && !strcmp(g, "half")) geo = 2;
-        if (g && !strcmp(g, "wave")) geo = 3;
-        if (g && !strcmp(g, "narrow")) geo = 5;
-        if (lp) geo = 0;
-        if (geo == 1 && fixed_lds_bytes<TW_WG_SPARSE, TW_NEAR_SPARSE>() + prog_lds > 160 * 1024) geo = 0;
+        int geo = lp ? TW_GEO_DENSE : R <= 4096 ? TW_GEO_WAVE : R < 65536 ? TW_GEO_NARROW
+                                    : s->run_capacity == 0 ? TW_GEO_COMPACT : TW_GEO_DENSE;
+        const std::pair<const char*, int> names[] = {{"dense", TW_GEO_DENSE}, {"compact", TW_GEO_COMPACT},
+                                                     {"sparse", TW_GEO_SPARSE}, {"half", TW_GEO_HALF},
+                                                     {"wave", TW_GEO_WAVE}, {"narrow", TW_GEO_NARROW}};
+        for (const auto& n : names)
+            if (g && !lp && !strcmp(g, n.first)) geo = n.second;
+        if (geo == TW_GEO_SPARSE && GeoSparse::LDS + prog_lds > 160 * 1024) geo = TW_GEO_DENSE;
         c->geo = geo;
     }
-    if (c->geo == 7) d.Cr = 0;  // far events: the HBM heap only
-    c->lds_bytes = (lp            ? fixed_lds_bytes<TW_WG_LP, TW_NEAR_LP, true>()
-                    : c->geo == 7 ? fixed_lds_bytes<TW_WG, TW_NEAR_COMPACT, false, false>()
-                    : c->geo == 1 ? fixed_lds_bytes<TW_WG_SPARSE, TW_NEAR_SPARSE>()
-                    : c->geo == 5 ? fixed_lds_bytes<TW_NARROW, TW_NEAR_CAP>()
-                                  : fixed_lds_bytes<TW_WG, TW_NEAR_CAP>()) +
-                   prog_lds;
-    if (c->geo == 3) c->lds_bytes = 0;  // the wave kernel reads the program image through the scalar cache
+    const bool wave = c->geo == TW_GEO_WAVE;
+    if (c->geo == TW_GEO_COMPACT) d.Cr = 0;  // far events: the HBM heap only
+    // (the wave kernel reads the program image through the scalar cache)
+    c->lds_bytes = wave ? 0 : with_geo(c, [](auto g) { return g.LDS; }) + prog_lds;
     if (c->lds_bytes > 160 * 1024) { free_all(c); return TW_ERR_INVALID; }  // program + constants must fit in LDS
-    {
-        // (the kernel and, for the lane-per-replica geometries, its fork-in-place variant)
-        auto lds = [&](const void* k) { return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                                    (int)c->lds_bytes); };
-        if (c->geo == 3) {
-        } else if (lp) {
-            HIPCHK(lds((const void*)tw_run_kernel<true, TW_WG_LP, TW_NEAR_LP>));
-            if (lpb) {  // the TRACE-recording instantiations (launch_run: every GS / PRW variant)
-                HIPCHK(lds((const void*)tw_run_kernel<true, TW_WG_LP, TW_NEAR_LP, 64, true, false, false, false, true>));
-                HIPCHK(lds((const void*)tw_run_kernel<true, TW_WG_LP, TW_NEAR_LP, 64, true, false, true, false, true>));
-                HIPCHK(lds((const void*)tw_run_kernel<true, TW_WG_LP, TW_NEAR_LP, 64, true, true, false, false, true>));
-                HIPCHK(lds((const void*)tw_run_kernel<true, TW_WG_LP, TW_NEAR_LP, 64, true, true, true, false, true>));
-            }
-        } else if (c->geo == 1) {
-            HIPCHK(lds((const void*)tw_run_kernel<false, TW_WG_SPARSE, TW_NEAR_SPARSE>));
-        } else if (c->geo == 2) {
-            HIPCHK(lds((const void*)tw_run_kernel<false, TW_WG, TW_NEAR_CAP, TW_HALF_LANES>));
-            HIPCHK(lds((const void*)tw_run_kernel<false, TW_WG, TW_NEAR_CAP, TW_HALF_LANES, true, false, false, true>));
-        } else if (c->geo == 5) {
-            HIPCHK(lds((const void*)tw_run_kernel<false, TW_NARROW, TW_NEAR_CAP, TW_NARROW>));
-            HIPCHK(lds((const void*)tw_run_kernel<false, TW_NARROW, TW_NEAR_CAP, TW_NARROW, true, false, false, true>));
-        } else if (c->geo == 7) {
-            HIPCHK(lds((const void*)tw_run_kernel<false, TW_WG, TW_NEAR_COMPACT, 64, false>));
-            HIPCHK(lds((const void*)tw_run_kernel<false, TW_WG, TW_NEAR_COMPACT, 64, false, false, false, true>));
-        } else {
-            HIPCHK(lds((const void*)tw_run_kernel<false, TW_WG, TW_NEAR_CAP>));
-            HIPCHK(lds((const void*)tw_run_kernel<false, TW_WG, TW_NEAR_CAP, 64, true, false, false, true>));
-        }
+    if (!wave) {  // every instantiation launch_run can pick
+        hipError_t he = hipSuccess;
+        with_geo(c, [&](auto g) {
+            each_kernel<decltype(g)>([&](RunKernel k, Variant) {
+                if (he == hipSuccess)
+                    he = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)c->lds_bytes);
+            });
+        });
+        HIPCHK(he);
     }
     int e;
 #define ALLOC(p, n) if ((e = dalloc(c, &p, (n))) != TW_OK) { free_all(c); return e; }
@@ -608,8 +569,8 @@ static int load_common(tw_shard* c, const tw_scenario_desc* s, bool lp, uint32_t
     ALLOC(d.free_stk, (size_t)d.S * R);
     ALLOC(d.far, (size_t)d.Q * R);
     ALLOC(d.runs, (size_t)(d.Cr ? TW_RUNS * (size_t)d.Cr : 1) * R);
-    if (c->geo == 3) d.wave_k = (uint32_t)wave_near_k(d.R);
-    ALLOC(d.near_spill, (size_t)(lp ? TW_NEAR_LP : c->geo == 1 ? TW_NEAR_SPARSE : c->geo == 3 ? wave_spill_entries(d.wave_k) : TW_NEAR_CAP) * R);
+    if (wave) d.wave_k = (uint32_t)wave_near_k(d.R);
+    ALLOC(d.near_spill, (size_t)(wave ? wave_spill_entries(d.wave_k) : with_geo(c, [](auto g) { return g.SPILL; })) * R);
     ALLOC(d.dummy, (size_t)TW_DUMMY_REC + R);
     ALLOC(d.nvars, (size_t)d.N * 4 * R);
     ALLOC(d.hash, (size_t)d.N * R);
@@ -772,7 +733,7 @@ static int load_common(tw_shard* c, const tw_scenario_desc* s, bool lp, uint32_t
     }
     d.msg_bytes = mbytes;
     d.link_bw = lbw;
-    if (c->geo == 3) {
+    if (wave) {
         std::vector<uint8_t> cls;
         classify_pcs(s, cls);
         uint8_t* pcl = nullptr;
@@ -793,34 +754,32 @@ static int load_common(tw_shard* c, const tw_scenario_desc* s, bool lp, uint32_t
             d.lpc_bat = bd;
         }
     }
-    c->sweep_on = true;
-    if (!lp && (c->geo == 0 || c->geo == 2 || c->geo == 5) && d.Cr) {
-        // the far-run geometries: kill stubs and their wake times (sweep_classify.hpp).
+    if (far_run_geo(c) && d.Cr) {
+        // kill stubs and their wake times (sweep_classify.hpp).
         // The scratch is optional: without it the context runs without sweeps
         SweepPlan plan = sweep_classify(s->insns, s->n_insns, s->consts, s->n_consts);
         uint32_t* stub = nullptr;
         uint32_t* acc = nullptr;
         unsigned long long* stats = nullptr;
-        if (!plan.times.empty() && (c->h_sw || hipHostMalloc((void**)&c->h_sw, 8 * SWS_COUNT) == hipSuccess) &&
+        if (!plan.times.empty() && (c->sw.h || hipHostMalloc((void**)&c->sw.h, 8 * SWS_COUNT) == hipSuccess) &&
             dalloc(c, &stub, plan.stub.size()) == TW_OK && dalloc(c, &acc, sweep_acc_words(d.R)) == TW_OK &&
             dalloc(c, &stats, SWS_COUNT) == TW_OK) {
             HIPCHK(hipMemcpy(stub, plan.stub.data(), 4 * plan.stub.size(), hipMemcpyHostToDevice));
             HIPCHK(hipMemsetAsync(stats, 0, 8 * SWS_COUNT, st));
-            c->sw.stub = stub;
-            c->sw.acc = acc;
-            c->sw.stats = stats;
-            c->sw.near_cap = TW_NEAR_CAP;
-            c->sw_times = plan.times;
+            c->sw.tab.stub = stub;
+            c->sw.tab.acc = acc;
+            c->sw.tab.stats = stats;
+            c->sw.tab.near_cap = TW_NEAR_CAP;
+            c->sw.times = plan.times;
         } else {
             (void)hipGetLastError();  // (a failed allocation is not an error of the load)
         }
     }
     // the send-free prefix (prefix_classify.hpp): replica contexts only
-    c->px_on = true;
-    c->px_t0 = lp ? 0 : prefix_t0(s->insns, s->n_insns, s->consts, s->n_consts, s->main_pc);
+    c->px.t0 = lp ? 0 : prefix_t0(s->insns, s->n_insns, s->consts, s->n_consts, s->main_pc);
     // (an image that never sends ends inside its prefix: the pilot would run the
     // first workgroup's replicas to the end, without sweeps, and be refused)
-    if (c->px_t0 == INT64_MAX) c->px_t0 = 0;
+    if (c->px.t0 == INT64_MAX) c->px.t0 = 0;
     d.insns = insns; d.consts = consts; d.lpc = lpc; d.out_off = out_off; d.link_dst = ldst; d.link_rev = lrev;
     d.link_table = ltab;
     c->main_pc = s->main_pc;
@@ -854,7 +813,7 @@ int sh_reset(tw_shard* c) {
     const Dev& d = c->d;
     const size_t R = d.R;
     hipStream_t st = c->stream;
-    c->sw_done = 0;
+    c->sw.done = 0;
     HIPCHK(hipMemsetAsync(d.nvars, 0, 32ull * d.N * R, st));
     HIPCHK(hipMemsetAsync(d.hash, 0, 8ull * d.N * R, st));
     HIPCHK(hipMemsetAsync(d.bind, 0, 4ull * d.N * R, st));
@@ -888,7 +847,7 @@ int sh_reset(tw_shard* c) {
                        (const int64_t*)c->main_regs, (const int64_t*)c->nv_init, (const uint32_t*)c->listen_init,
                        c->lp ? 1 : 0, c->seq0, c->tid0);
     HIPCHK(hipGetLastError());
-    c->fresh = true;
+    c->px.fresh = true;
     return TW_OK;
 }
 
@@ -897,74 +856,77 @@ static int lpb_run(tw_shard* c, tw_stats* out);
 
 // one launch of the context's event kernel to t_end (grid: launch_run)
 static int launch_event(tw_shard* c, hipStream_t st, int64_t t_end, uint64_t limit, uint32_t budget, uint32_t grid = 0) {
-    if (c->lp)
-        launch_run<true, TW_WG_LP, TW_NEAR_LP>(c, st, t_end, limit, budget);
-    else if (c->geo == 3)
+    if (c->geo == TW_GEO_WAVE)
         HIPCHK(wave_launch(c->d, c->d_dev, st, t_end, limit, 1u << 16));
-    else if (c->geo == 1)
-        launch_run<false, TW_WG_SPARSE, TW_NEAR_SPARSE>(c, st, t_end, limit, budget, grid);
-    else if (c->geo == 2)
-        launch_run<false, TW_WG, TW_NEAR_CAP, TW_HALF_LANES>(c, st, t_end, limit, budget, grid);
-    else if (c->geo == 5)
-        launch_run<false, TW_NARROW, TW_NEAR_CAP, TW_NARROW>(c, st, t_end, limit, budget, grid);
-    else if (c->geo == 7)
-        launch_run<false, TW_WG, TW_NEAR_COMPACT, 64, false>(c, st, t_end, limit, budget, grid);
     else
-        launch_run<false, TW_WG, TW_NEAR_CAP>(c, st, t_end, limit, budget, grid);
+        with_geo(c, [&](auto g) { launch_run<decltype(g)>(c, st, t_end, limit, budget, grid); });
     HIPCHK(hipGetLastError());
     return TW_OK;
 }
 
+// A sweep time T of the image (Sweep::times[ix]) that lies within the run
+struct Stop { int64_t T; uint32_t ix; };
+// ... and, as the stop ahead of a round: the run's segment it ends, the run's own end
+struct SweepAt { int64_t T, run_end; uint32_t seg; };
+
+// One round of tw_run: n launches of the event kernel to t_end, each behind a
+// cleared n_active and timed; with a sweep stop ahead, each followed by the
+// sweep kernels, timed as a step of their own (fired or not: their time is
+// listed behind their launch's, `launches` counts the event kernel's).  Then
+// the host's check: n_active and the sweeps' words copied, the stream
+// synchronised, the times read (LaunchTimes: in the order recorded).
+static int run_round(tw_shard* c, int n, int64_t t_end, uint64_t limit, uint32_t budget, uint32_t grid,
+                     const SweepAt* sw, uint32_t* launches) {
+    const Dev& d = c->d;
+    hipStream_t st = c->stream;
+    for (int i = 0; i < n; ++i) {
+        HIPCHK(hipMemsetAsync(d.n_active, 0, 4, st));
+        if (c->lp) HIPCHK(hipMemsetAsync(d.next_t, 0xFF, 8, st));
+        int rc = c->times.timed(st, [&]() -> int { return launch_event(c, st, t_end, limit, budget, grid); });
+        if (rc) return rc;
+        ++*launches;
+        if (!sw) continue;
+        rc = c->times.timed(st, [&]() -> int {
+            HIPCHK(sweep_launch(d, c->sw.tab, st, sw->T, limit, sw->run_end, sw->seg));
+            return TW_OK;
+        }, &c->sw.ms);
+        if (rc) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(c->h_active, d.n_active, 4, hipMemcpyDeviceToHost, st));
+    if (sw) HIPCHK(hipMemcpyAsync(c->sw.h, c->sw.tab.stats, 8 * SWS_COUNT, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return c->times.read();
+}
+
 // The send-free prefix of a fresh run.  With a snapshot cached
-// for the context's tie mode and counter bases, its apply goes onto the stream
-// (between c->px_ev: the caller reads its time at its first sync).  Without
+// for the context's tie mode and counter bases, its apply goes onto the stream,
+// timed (read at the caller's first round: the list's next entry).  Without
 // one, the first workgroup alone runs to T0 - 1 -- the pilot: the ordinary
-// run's first segment on a grid of one, no sweeps behind it --, replica 0 is
+// run's rounds on a grid of one, no sweeps behind them --, replica 0 is
 // checked to have run as every replica must (still running, under the event
 // cap, no message counted, no send ordinal taken), its parked state becomes
 // the snapshot and is applied to every replica, the pilot's own included.  A
 // pilot that fails the check is remembered as "no prefix" for the key; its
 // replicas are simply ahead of the others and the run goes on as ever.
 // *applied: the apply is on the stream.
-static int run_prefix(tw_shard* c, uint64_t limit, uint32_t budget, uint32_t* launches, double* kms, bool* applied) {
+static int run_prefix(tw_shard* c, uint64_t limit, uint32_t budget, uint32_t* launches, bool* applied) {
     const Dev& d = c->d;
     hipStream_t st = c->stream;
+    Prefix& px = c->px;
     *applied = false;
-    for (int i = 0; i < 2; ++i)
-        if (!c->px_ev[i]) HIPCHK(hipEventCreate(&c->px_ev[i]));
-    const bool hit = c->px_have && c->px_tie == d.tie_mode && c->px_seq0 == c->seq0 && c->px_tid0 == c->tid0;
-    if (hit && !c->px_ok) { c->px_last = TW_PREFIX_REFUSED; return TW_OK; }
-    if (hit && limit < c->px_events) return TW_OK;  // (the cap falls inside the prefix: the ordinary run)
+    const bool hit = px.snap.have && px.snap.tie == d.tie_mode && px.snap.seq0 == c->seq0 && px.snap.tid0 == c->tid0;
+    if (hit && !px.snap.ok) { px.last = TW_PREFIX_REFUSED; return TW_OK; }
+    if (hit && limit < px.snap.events) return TW_OK;  // (the cap falls inside the prefix: the ordinary run)
     if (!hit) {
         HIPCHK(hipStreamSynchronize(st));
-        px_drop(c);
-        c->px_have = true;
-        c->px_tie = d.tie_mode; c->px_seq0 = c->seq0; c->px_tid0 = c->tid0;
-        c->px_last = TW_PREFIX_REFUSED;
-        const int per_check = 4;
-        while (c->ev_pool.size() < 2 * (size_t)per_check) {
-            hipEvent_t e;
-            HIPCHK(hipEventCreate(&e));
-            c->ev_pool.push_back(e);
-        }
+        px.drop();
+        px.snap.have = true;
+        px.snap.tie = d.tie_mode; px.snap.seq0 = c->seq0; px.snap.tid0 = c->tid0;
+        px.last = TW_PREFIX_REFUSED;
         bool parked = false;
         for (int round = 0; round < (1 << 20) && !parked; ++round) {
-            for (int i = 0; i < per_check; ++i) {
-                HIPCHK(hipMemsetAsync(d.n_active, 0, 4, st));
-                HIPCHK(hipEventRecord(c->ev_pool[2 * i], st));
-                int rc = launch_event(c, st, c->px_t0 - 1, limit, budget, 1u);
-                if (rc) return rc;
-                HIPCHK(hipEventRecord(c->ev_pool[2 * i + 1], st));
-                ++*launches;
-            }
-            HIPCHK(hipMemcpyAsync(c->h_active, d.n_active, 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            for (int i = 0; i < per_check; ++i) {
-                float ms = 0.f;
-                HIPCHK(hipEventElapsedTime(&ms, c->ev_pool[2 * i], c->ev_pool[2 * i + 1]));
-                c->launch_ms.push_back(ms);
-                *kms += ms;
-            }
+            int rc = run_round(c, 4, px.t0 - 1, limit, budget, 1u, nullptr, launches);
+            if (rc) return rc;
             parked = *c->h_active == 0;
         }
         if (!parked) return TW_OK;
@@ -988,33 +950,64 @@ static int run_prefix(tw_shard* c, uint64_t limit, uint32_t budget, uint32_t* la
             if (drows) (void)hipFree(drows);
             return TW_OK;
         }
-        c->px.rows = (const tw::PrefixRow*)drows;
-        c->px.snap = (uint8_t*)dsnap;
-        c->px.n_rows = (uint32_t)rows.size();
+        px.snap.tab.rows = (const tw::PrefixRow*)drows;
+        px.snap.tab.snap = (uint8_t*)dsnap;
+        px.snap.tab.n_rows = (uint32_t)rows.size();
         HIPCHK(hipMemcpy(drows, rows.data(), sizeof(tw::PrefixRow) * rows.size(), hipMemcpyHostToDevice));
         uint32_t mx = 0;
         for (const tw::PrefixRow& r : rows) mx = r.es > mx ? r.es : mx;
-        c->px_max_es = mx;
-        c->px_events = sc[SC_EVENTS];
-        c->px_bytes = bytes;
-        HIPCHK(prefix_take(c->px, st));
-        c->px_ok = true;
+        px.snap.max_es = mx;
+        px.snap.events = sc[SC_EVENTS];
+        px.snap.bytes = bytes;
+        HIPCHK(prefix_take(px.snap.tab, st));
+        px.snap.ok = true;
     }
-    HIPCHK(hipEventRecord(c->px_ev[0], st));
-    HIPCHK(prefix_apply(c->px, d.R, c->px_max_es, st));
-    HIPCHK(hipEventRecord(c->px_ev[1], st));
-    c->px_last = hit ? TW_PREFIX_APPLIED : TW_PREFIX_PILOTED;
+    int rc = c->times.timed(st, [&]() -> int {
+        HIPCHK(prefix_apply(px.snap.tab, d.R, px.snap.max_es, st));
+        return TW_OK;
+    }, &px.ms);
+    if (rc) return rc;
+    px.last = hit ? TW_PREFIX_APPLIED : TW_PREFIX_PILOTED;
     *applied = true;
     return TW_OK;
 }
 
+// tw_run's statistics: reduced on the device from the events column taken at
+// the run's start (tw_stats_kernel), with the run's launches and times
+static int reduce_stats(tw_shard* c, uint32_t launches, std::chrono::steady_clock::time_point w0, tw_stats* out) {
+    const Dev& d = c->d;
+    hipStream_t st = c->stream;
+    std::memset(out, 0, sizeof(*out));
+    HIPCHK(hipMemsetAsync(c->st_out, 0, 64, st));
+    hipLaunchKernelGGL(tw_stats_kernel, dim3((uint32_t)((d.R + 255) / 256)), dim3(256), 0, st, d,
+                       (const uint64_t*)c->st_ev0, c->st_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->h_st, c->st_out, 64, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const unsigned long long* h = c->h_st;
+    out->events = h[0];
+    out->delivered = h[1];
+    out->dropped = h[2];
+    out->undeliverable = h[3];
+    out->max_final_t = (int64_t)h[4];
+    out->replicas_done = (uint32_t)h[5];
+    out->replicas_error = (uint32_t)h[6];
+    out->sends = out->delivered + out->dropped + out->undeliverable;
+    out->launches = launches;
+    out->kernel_ms = c->times.total;
+    out->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+    return TW_OK;
+}
+
+// tw_run: take the prefix, plan the sweep stops, run rounds until every
+// replica is quiet, reduce the statistics.
 int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
     if (!c) return TW_ERR_INVALID;
     if (!c->loaded) return TW_ERR_STATE;
-    const bool was_fresh = c->fresh;
-    c->fresh = false;
-    c->px_last = TW_PREFIX_NOT_ELIGIBLE;
-    c->px_ms = 0.0;
+    const bool was_fresh = c->px.fresh;
+    c->px.fresh = false;
+    c->px.last = TW_PREFIX_NOT_ELIGIBLE;
+    c->px.ms = 0.0;
     if (c->lpb) {
         // the batched window loop runs every replica to quiescence
         if (t_end_us != INT64_MAX || max_events != UINT64_MAX) return TW_ERR_INVALID;
@@ -1040,7 +1033,7 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
                                   st));
     }
     const uint64_t limit = max_events;  // cumulative per-replica cap
-    c->launch_ms.clear();
+    c->times.start();
     if (c->lp) {
         // a new window: serve the list built since the last call (nodes with a
         // live thread or new records); start an empty one for the next call
@@ -1060,20 +1053,18 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
     // window is almost always done after one launch
     const int per_check = c->lp ? 1 : 4;
     uint32_t launches = 0;
-    double kms = 0.0;
-    bool quiet = false;
+    const bool swept_order = far_run_geo(c) && ordered_ties(c);
     // the send-free prefix: a fresh replica run that reaches T0 - 1
     // starts from the snapshot of that moment instead of popping its way there
-    bool px_pending = false;
-    if (was_fresh && c->px_on && !c->lp && (c->geo == 0 || c->geo == 2 || c->geo == 5) &&
-        (d.tie_mode == TW_TIE_FIFO || d.tie_mode == TW_TIE_FORKFIRST) && d.trace_cap == 0 && !c->main_regs &&
-        c->px_t0 >= 1 && t_end_us >= c->px_t0 - 1) {
-        int rc = run_prefix(c, limit, budget, &launches, &kms, &px_pending);
+    if (was_fresh && c->px.on && swept_order && d.trace_cap == 0 && !c->main_regs && c->px.t0 >= 1 &&
+        t_end_us >= c->px.t0 - 1) {
+        bool applied = false;
+        int rc = run_prefix(c, limit, budget, &launches, &applied);
         if (rc) return rc;
         // (sweep times inside the prefix: the snapshot is past them)
-        if (px_pending)
-            for (uint32_t i = 0; i < c->sw_times.size(); ++i)
-                if (c->sw_times[i] <= c->px_t0 - 1) c->sw_done |= 1u << i;
+        if (applied)
+            for (uint32_t i = 0; i < c->sw.times.size(); ++i)
+                if (c->sw.times[i] <= c->px.t0 - 1) c->sw.done |= 1u << i;
     }
     // killThread sweeps: the run is split at every sweep time T of
     // the image that lies within it.  While such a stop is ahead, the event
@@ -1085,103 +1076,37 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
     // No launch and no host round trip is added to a run whose replicas all
     // end in the sweep (C3): the segment's remaining launches find nothing to
     // do, and the sweep reports that no replica has work left.
-    struct Stop { int64_t T; uint32_t ix; };
     std::vector<Stop> stops;
-    c->sw_last[0] = c->sw_last[1] = c->sw_last[2] = 0;
-    c->sw_ms = 0.0;
-    if (!c->lp && c->sweep_on && c->sw.stub && (c->geo == 0 || c->geo == 2 || c->geo == 5) &&
-        (d.tie_mode == TW_TIE_FIFO || d.tie_mode == TW_TIE_FORKFIRST)) {
-        for (uint32_t i = 0; i < c->sw_times.size(); ++i) {
-            const int64_t T = c->sw_times[i];
-            if (T >= 1 && T <= t_end_us && !((c->sw_done >> i) & 1u)) stops.push_back(Stop{T, i});
+    c->sw.last[0] = c->sw.last[1] = c->sw.last[2] = 0;
+    c->sw.ms = 0.0;
+    if (c->sw.on && c->sw.tab.stub && swept_order) {
+        for (uint32_t i = 0; i < c->sw.times.size(); ++i) {
+            const int64_t T = c->sw.times[i];
+            if (T >= 1 && T <= t_end_us && !((c->sw.done >> i) & 1u)) stops.push_back(Stop{T, i});
         }
-        if (!stops.empty()) HIPCHK(hipMemsetAsync(c->sw.stats, 0, 8 * SWS_COUNT, st));
+        if (!stops.empty()) HIPCHK(hipMemsetAsync(c->sw.tab.stats, 0, 8 * SWS_COUNT, st));
     }
-    const size_t sw_ev0 = 2 * (size_t)per_check;  // the sweeps' event pairs, after the launches'
+    bool quiet = false;
     size_t seg = 0;
-    for (int round = 0; round < (1 << 20); ++round) {
+    for (int round = 0; round < (1 << 20) && !quiet; ++round) {
         const bool to_sweep = seg < stops.size();
-        const int64_t te_seg = to_sweep ? stops[seg].T - 1 : t_end_us;
-        size_t need = 4 * (size_t)per_check;
-        while (c->ev_pool.size() < need) {
-            hipEvent_t e;
-            HIPCHK(hipEventCreate(&e));
-            c->ev_pool.push_back(e);
+        const SweepAt at{to_sweep ? stops[seg].T : 0, t_end_us, (uint32_t)seg};
+        int rc = run_round(c, per_check, to_sweep ? at.T - 1 : t_end_us, limit, budget, 0, to_sweep ? &at : nullptr,
+                           &launches);
+        if (rc) return rc;
+        if (!to_sweep) {
+            quiet = *c->h_active == 0;
+        } else if (c->sw.h[SWS_FIRED] > seg) {
+            c->sw.done |= 1u << stops[seg].ix;
+            for (int k = 0; k < 3; ++k) c->sw.last[k] = c->sw.h[k];
+            ++seg;
+            // the last stop swept and no replica has work left before t_end: done
+            quiet = seg == stops.size() && c->sw.h[SWS_LEFT] == 0;
         }
-        for (int i = 0; i < per_check; ++i) {
-            HIPCHK(hipMemsetAsync(d.n_active, 0, 4, st));
-            if (c->lp) HIPCHK(hipMemsetAsync(d.next_t, 0xFF, 8, st));
-            HIPCHK(hipEventRecord(c->ev_pool[2 * i], st));
-            {
-                int rc = launch_event(c, st, te_seg, limit, budget);
-                if (rc) return rc;
-            }
-            HIPCHK(hipEventRecord(c->ev_pool[2 * i + 1], st));
-            ++launches;
-            if (to_sweep) {
-                HIPCHK(hipEventRecord(c->ev_pool[sw_ev0 + 2 * i], st));
-                HIPCHK(sweep_launch(c->d, c->sw, st, stops[seg].T, limit, t_end_us, (uint32_t)seg));
-                HIPCHK(hipEventRecord(c->ev_pool[sw_ev0 + 2 * i + 1], st));
-            }
-        }
-        HIPCHK(hipMemcpyAsync(c->h_active, d.n_active, 4, hipMemcpyDeviceToHost, st));
-        if (to_sweep) HIPCHK(hipMemcpyAsync(c->h_sw, c->sw.stats, 8 * SWS_COUNT, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (px_pending) {
-            // (the prefix apply in front of this round's first launch: device time of the step)
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, c->px_ev[0], c->px_ev[1]));
-            c->launch_ms.push_back(ms);
-            kms += ms;
-            c->px_ms = ms;
-            px_pending = false;
-        }
-        for (int i = 0; i < per_check; ++i) {
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, c->ev_pool[2 * i], c->ev_pool[2 * i + 1]));
-            c->launch_ms.push_back(ms);
-            kms += ms;
-            if (to_sweep) {
-                // (the sweep kernels behind this launch, fired or not: device time of the
-                // step, listed with the launches; `launches` counts the event kernel's)
-                HIPCHK(hipEventElapsedTime(&ms, c->ev_pool[sw_ev0 + 2 * i], c->ev_pool[sw_ev0 + 2 * i + 1]));
-                c->launch_ms.push_back(ms);
-                kms += ms;
-                c->sw_ms += ms;
-            }
-        }
-        if (to_sweep) {
-            if (c->h_sw[SWS_FIRED] > seg) {
-                c->sw_done |= 1u << stops[seg].ix;
-                for (int k = 0; k < 3; ++k) c->sw_last[k] = c->h_sw[k];
-                ++seg;
-                // the last stop swept and no replica has work left before t_end: done
-                if (seg == stops.size() && c->h_sw[SWS_LEFT] == 0) { quiet = true; break; }
-            }
-            continue;
-        }
-        if (*c->h_active == 0) { quiet = true; break; }
     }
     if (out) {
-        std::memset(out, 0, sizeof(*out));
-        HIPCHK(hipMemsetAsync(c->st_out, 0, 64, st));
-        hipLaunchKernelGGL(tw_stats_kernel, dim3((uint32_t)((d.R + 255) / 256)), dim3(256), 0, st, d,
-                           (const uint64_t*)c->st_ev0, c->st_out);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(c->h_st, c->st_out, 64, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        const unsigned long long* h = c->h_st;
-        out->events = h[0];
-        out->delivered = h[1];
-        out->dropped = h[2];
-        out->undeliverable = h[3];
-        out->max_final_t = (int64_t)h[4];
-        out->replicas_done = (uint32_t)h[5];
-        out->replicas_error = (uint32_t)h[6];
-        out->sends = out->delivered + out->dropped + out->undeliverable;
-        out->launches = launches;
-        out->kernel_ms = kms;
-        out->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+        int rc = reduce_stats(c, launches, w0, out);
+        if (rc) return rc;
     }
     return quiet ? TW_OK : TW_ERR_INCOMPLETE;
 }
@@ -1281,9 +1206,9 @@ int sh_set_tie_mode(tw_shard* c, uint32_t mode) {
     if (mode > TW_TIE_FORKFIRST) return TW_ERR_INVALID;
     // a forked child first: the lane-per-replica kernels (their fork_in_place);
     // the wave and logical-process kernels keep the other orders
-    if (mode == TW_TIE_FORKFIRST && (c->lp || c->geo == 3)) return TW_ERR_INVALID;
+    if (mode == TW_TIE_FORKFIRST && (c->lp || c->geo == TW_GEO_WAVE)) return TW_ERR_INVALID;
     if (mode == TW_TIE_PQUEUE) {
-        if (c->lp || c->geo != 3) return TW_ERR_INVALID;  // the wave kernel only
+        if (c->lp || c->geo != TW_GEO_WAVE) return TW_ERR_INVALID;  // the wave kernel only
         HIPCHK(hipSetDevice(c->device));
         HIPCHK(hipStreamSynchronize(c->stream));
         Dev& d = c->d;
@@ -1299,7 +1224,7 @@ int sh_set_tie_mode(tw_shard* c, uint32_t mode) {
     c->d.tie_mode = mode;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    px_drop(c);
+    c->px.drop();
     return TW_OK;
 }
 
@@ -1307,10 +1232,10 @@ int sh_set_counter_base(tw_shard* c, uint32_t seq0, uint32_t tid0) {
     if (!c || tid0 == 0) return TW_ERR_INVALID;
     c->seq0 = seq0;
     c->tid0 = tid0;
-    if (c->px_have) {
+    if (c->px.snap.have) {
         HIPCHK(hipSetDevice(c->device));
         HIPCHK(hipStreamSynchronize(c->stream));
-        px_drop(c);
+        c->px.drop();
     }
     return TW_OK;
 }
@@ -1320,18 +1245,18 @@ int sh_set_counter_base(tw_shard* c, uint32_t seq0, uint32_t tid0) {
 int sh_set_prefix(tw_shard* c, int on) {
     if (!c) return TW_ERR_INVALID;
     if (!c->loaded) return TW_ERR_STATE;
-    c->px_on = on != 0;
+    c->px.on = on != 0;
     return TW_OK;
 }
 
 int sh_prefix_stats(tw_shard* c, int64_t* t0, uint64_t* events, uint64_t* bytes, uint32_t* last, double* ms) {
     if (!c) return TW_ERR_INVALID;
     if (!c->loaded) return TW_ERR_STATE;
-    if (t0) *t0 = c->px_t0;
-    if (events) *events = c->px_ok ? c->px_events : 0;
-    if (bytes) *bytes = c->px_ok ? c->px_bytes : 0;
-    if (last) *last = c->px_last;
-    if (ms) *ms = c->px_ms;
+    if (t0) *t0 = c->px.t0;
+    if (events) *events = c->px.snap.ok ? c->px.snap.events : 0;
+    if (bytes) *bytes = c->px.snap.ok ? c->px.snap.bytes : 0;
+    if (last) *last = c->px.last;
+    if (ms) *ms = c->px.ms;
     return TW_OK;
 }
 
@@ -1340,17 +1265,17 @@ int sh_prefix_stats(tw_shard* c, int64_t* t0, uint64_t* events, uint64_t* bytes,
 int sh_set_sweep(tw_shard* c, int on) {
     if (!c) return TW_ERR_INVALID;
     if (!c->loaded) return TW_ERR_STATE;
-    c->sweep_on = on != 0;
+    c->sw.on = on != 0;
     return TW_OK;
 }
 
 int sh_sweep_stats(tw_shard* c, uint64_t* killers, uint64_t* victims, uint64_t* refused, double* ms) {
     if (!c) return TW_ERR_INVALID;
     if (!c->loaded) return TW_ERR_STATE;
-    if (killers) *killers = c->sw_last[0];
-    if (victims) *victims = c->sw_last[1];
-    if (refused) *refused = c->sw_last[2];
-    if (ms) *ms = c->sw_ms;
+    if (killers) *killers = c->sw.last[0];
+    if (victims) *victims = c->sw.last[1];
+    if (refused) *refused = c->sw.last[2];
+    if (ms) *ms = c->sw.ms;
     return TW_OK;
 }
 
@@ -1656,7 +1581,7 @@ int sh_lp_tick(tw_shard* c) {
     // the window comes from the device (tw_run_kernel reads c.win); launch
     // arguments are captured at enqueue, so d.win is set only around it
     c->d.win = c->win_buf;
-    launch_run<true, TW_WG_LP, TW_NEAR_LP>(c, st, 0, UINT64_MAX, c->lp_budget);
+    launch_run<GeoLP>(c, st, 0, UINT64_MAX, c->lp_budget);
     c->d.win = nullptr;
     HIPCHK(hipGetLastError());
     if (c->ex_world > 1 && d.carry) {  // the previous tick's carry claims block slots first
@@ -1857,24 +1782,19 @@ static int lpb_run(tw_shard* c, tw_stats* out) {
         }
     }
     c->lpb_fresh = false;
-    while (c->ev_pool.size() < 2) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        c->ev_pool.push_back(e);
-    }
     int rc = sh_lp_loop_begin(c);
     if (rc) return rc;
-    HIPCHK(hipEventRecord(c->ev_pool[0], c->stream));
+    c->times.start();
     tw_lp_state ls{};
-    rc = sh_lp_run_windows(c, 1ull << 40, &ls);
-    HIPCHK(hipEventRecord(c->ev_pool[1], c->stream));
+    int rcw = TW_OK;  // (the loop's own result: its time is taken either way)
+    rc = c->times.timed(c->stream, [&]() -> int { rcw = sh_lp_run_windows(c, 1ull << 40, &ls); return TW_OK; });
+    if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev_pool[0], c->ev_pool[1]));
-    c->launch_ms.assign(1, ms);
+    rc = c->times.read();
+    if (rc) return rc;
     c->lpb_windows = ls.windows;
     c->lpb_ticks = ls.ticks;
-    if (rc) return rc;
+    if (rcw) return rcw;
     if (out) {
         std::memset(out, 0, sizeof(*out));
         std::vector<tw_replica_result> rr(c->n_rep);
@@ -1891,7 +1811,7 @@ static int lpb_run(tw_shard* c, tw_stats* out) {
         }
         out->sends = out->delivered + out->dropped + out->undeliverable;
         out->launches = 1;  // the window loop, timed as one (tw_last_launch_ms)
-        out->kernel_ms = ms;
+        out->kernel_ms = c->times.total;
         out->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
     }
     return TW_OK;
@@ -2047,8 +1967,9 @@ int sh_measure(tw_shard* c, const tw_measure_spec* spec, tw_measure_out* total, 
 
 int sh_last_launch_ms(tw_shard* c, double* out, size_t cap) {
     if (!c || !out) return TW_ERR_INVALID;
-    size_t n = c->launch_ms.size() < cap ? c->launch_ms.size() : cap;
-    for (size_t i = 0; i < n; ++i) out[i] = c->launch_ms[i];
+    const std::vector<double>& ms = c->times.ms;
+    size_t n = ms.size() < cap ? ms.size() : cap;
+    for (size_t i = 0; i < n; ++i) out[i] = ms[i];
     return (int)n;
 }
 
