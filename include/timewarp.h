@@ -435,10 +435,37 @@ typedef struct tw_measure_out {
     int64_t  sum_us;               /* two's-complement sum of the pairs' latencies */
 } tw_measure_out;
 
-/* tag_from + tag_to records one replica may hold: the join sorts a replica's
- * keys in one workgroup's LDS (there is no global-memory sort path). */
+/* tag_from + tag_to records one replica may hold by default: the join sorts a
+ * replica's keys in one workgroup's LDS.  tw_set_measure_keys raises the limit,
+ * up to TW_MEASURE_MAX_KEYS_LARGE. */
 #define TW_MEASURE_MAX_KEYS 2048u
+#define TW_MEASURE_MAX_KEYS_LARGE 4194304u   /* 4,096 buckets of 1,024 keys in the mean */
 #define TW_MEASURE_MAX_BINS 4096u
+
+/* The number of matching (tag_from or tag_to) records one non-truncated replica
+ * may hold in tw_measure: TW_MEASURE_MAX_KEYS (the default) ..
+ * TW_MEASURE_MAX_KEYS_LARGE; anything else is TW_ERR_INVALID and leaves the
+ * setting as it was.  A setting of the context: it applies to every shard and
+ * survives tw_load, tw_reset and tw_set_trace.
+ * Replicas with at most TW_MEASURE_MAX_KEYS matching records are joined in LDS
+ * as before.  Larger ones, up to the setting, are joined through device memory:
+ * their keys are hash-partitioned by id into buckets of 1,024 keys in the mean
+ * (the next power of two >= ceil(m / 1024) buckets for a replica of m keys),
+ * and each bucket is aggregated in an LDS table of 2,048 distinct ids.  The
+ * results are the same function of the records whichever way a replica goes.
+ * It is opt-in because that path allocates device scratch for the duration of
+ * the call, per shard, beyond the LDS path's:
+ *     64 + 28 * replicas of the shard           (as soon as some replica is large)
+ *   + 24 * buckets + 16 * keys                  (of the large replicas)
+ * bytes; a failed allocation is TW_ERR_OOM, nothing is written and the context
+ * stays usable.  A replica over the setting makes tw_measure return
+ * TW_ERR_INVALID, decided on the device before the bucket and key scratch is
+ * allocated.  The id hash is a fixed bijective mixer, so ordinary id families
+ * (consecutive, strided, negative) fill the buckets evenly; ids chosen against
+ * it can put more than 2,048 distinct ids into one bucket: tw_measure then
+ * returns TW_ERR_INVALID with nothing written (a status, the context stays
+ * usable).  An id that repeats any number of times is one `repeated`. */
+int tw_set_measure_keys(tw_ctx* ctx, uint32_t max_keys);
 
 /* Blocking, stream-ordered after the last tw_run; changes no state (results,
  * hashes and traces read afterwards are what they were) and may be called
@@ -451,7 +478,8 @@ typedef struct tw_measure_out {
  * measured like a replica context),
  * for a bad spec (tag_from == tag_to, n_bins == 0 or > TW_MEASURE_MAX_BINS,
  * bin_us < 1, reserved != 0), for another n, and when some non-truncated
- * replica holds more than TW_MEASURE_MAX_KEYS matching records -- decided on
+ * replica holds more matching records than the context allows
+ * (TW_MEASURE_MAX_KEYS unless tw_set_measure_keys raised it) -- decided on
  * the device before the join runs; no output is written then.  A context over
  * several devices runs every shard and combines on the host.  A rank context
  * (tw_create_rank) measures this rank's replicas only: there is no job-wide
@@ -462,6 +490,10 @@ int tw_measure(tw_ctx* ctx, const tw_measure_spec* spec, tw_measure_out* total,
 /* Device time (ms, HIP events) of the kernels of the last tw_measure: the
  * slowest shard's. */
 int tw_measure_ms(tw_ctx* ctx, double* kernel_ms);
+/* ... and by kernel, that shard's: count, plan, partition count, bucket
+ * ranges, partition scatter, LDS join, bucket join (0 for those that did not
+ * run).  Writes min(cap, 7) entries and returns how many. */
+int tw_measure_phases_ms(tw_ctx* ctx, double* ms, size_t cap);
 
 /* Tie-order audit: run every replica (as tw_run with t_end_us / max_events)
  * under each probe order p in 1..probes (TW_TIE_LIFO, TW_TIE_SCRAMBLE), then

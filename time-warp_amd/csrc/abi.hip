@@ -81,6 +81,9 @@ struct tw_ctx {
     long test_fail_at = 0;
     std::atomic<long> test_calls{0};
     double measure_ms = 0.0;  // kernels of the last tw_measure (tw_measure_ms)
+    double measure_phase_ms[MEASURE_PHASES] = {};  // ... by kernel (tw_measure_phases_ms): the slowest shard's
+    // tw_set_measure_keys, and the testing hook TW_TEST_MEASURE (test_hook_init)
+    MeasureCfg measure_cfg{TW_MEASURE_MAX_KEYS, TW_MEASURE_MAX_KEYS, 1024};
 };
 
 namespace {
@@ -96,6 +99,20 @@ int comm_fail(ncclResult_t r, const char* what) {
 void test_hook_init(tw_ctx* c) {
     const char* e = getenv("TW_TEST_FAIL_NCCL");
     c->test_fail_at = e ? atol(e) : 0;
+    // TW_TEST_MEASURE=lds_keys:bucket_keys sends tw_measure's replicas with
+    // more than lds_keys (0 .. TW_MEASURE_MAX_KEYS) matching records through
+    // the partition path, with buckets of bucket_keys (1 .. 2^22) keys in the
+    // mean: small shapes reach that path, and one bucket can be overfilled.
+    // What tw_set_measure_keys accepts is unchanged.
+    if (const char* m = getenv("TW_TEST_MEASURE")) {
+        char* end = nullptr;
+        const long lds = strtol(m, &end, 10);
+        const long bk = (end && *end == ':') ? strtol(end + 1, nullptr, 10) : 0;
+        if (lds >= 0 && lds <= (long)TW_MEASURE_MAX_KEYS && bk >= 1 && bk <= (1l << 22)) {
+            c->measure_cfg.lds_keys = (uint32_t)lds;
+            c->measure_cfg.bucket_keys = (uint32_t)bk;
+        }
+    }
 }
 bool nccl_test_fail(tw_ctx* c) { return c->test_fail_at > 0 && ++c->test_calls == c->test_fail_at; }
 // (in a function of the context c: a failure marks it unusable)
@@ -624,15 +641,17 @@ int tw_measure(tw_ctx* c, const tw_measure_spec* spec, tw_measure_out* total, ui
     measure_empty(&tot);
     std::vector<uint64_t> h(spec->n_bins, 0), sh_h(spec->n_bins);
     std::vector<tw_measure_out> per(per_replica ? n : 0), sh_per;
-    double ms = 0.0;
+    double ms = 0.0, phase[MEASURE_PHASES] = {}, sph[MEASURE_PHASES];
     size_t off = 0;
     for (tw_shard* s : c->sh) {
         const size_t k = sh_replicas(s);
         tw_measure_out st;
         double sms = 0.0;
         if (per_replica) sh_per.resize(k);
-        int rc = sh_measure(s, spec, &st, sh_h.data(), per_replica ? sh_per.data() : nullptr, &sms);
+        int rc = sh_measure(s, spec, c->measure_cfg, &st, sh_h.data(), per_replica ? sh_per.data() : nullptr, &sms,
+                            sph);
         if (rc) return rc;
+        if (sms > ms || off == 0) std::copy(sph, sph + MEASURE_PHASES, phase);
         if (!measure_combine(&tot, h.data(), spec->n_bins, per_replica ? per.data() : nullptr, n, &st, sh_h.data(),
                              per_replica ? sh_per.data() : nullptr, off, k))
             return TW_ERR_INVALID;
@@ -643,7 +662,21 @@ int tw_measure(tw_ctx* c, const tw_measure_spec* spec, tw_measure_out* total, ui
     if (hist) std::memcpy(hist, h.data(), (size_t)spec->n_bins * 8);
     if (per_replica) std::memcpy(per_replica, per.data(), n * sizeof(tw_measure_out));
     c->measure_ms = ms;
+    std::copy(phase, phase + MEASURE_PHASES, c->measure_phase_ms);
     return TW_OK;
+}
+
+int tw_set_measure_keys(tw_ctx* c, uint32_t max_keys) {
+    if (!c || max_keys < TW_MEASURE_MAX_KEYS || max_keys > TW_MEASURE_MAX_KEYS_LARGE) return TW_ERR_INVALID;
+    c->measure_cfg.max_keys = max_keys;  // (of the context: every shard's tw_measure gets it)
+    return TW_OK;
+}
+
+int tw_measure_phases_ms(tw_ctx* c, double* ms, size_t cap) {
+    if (!c || !ms) return TW_ERR_INVALID;
+    const size_t n = cap < (size_t)MEASURE_PHASES ? cap : (size_t)MEASURE_PHASES;
+    std::copy(c->measure_phase_ms, c->measure_phase_ms + n, ms);
+    return (int)n;
 }
 
 int tw_measure_ms(tw_ctx* c, double* kernel_ms) {

@@ -1953,16 +1953,16 @@ int sh_measure_state(tw_shard* c) {
     return TW_OK;
 }
 
-int sh_measure(tw_shard* c, const tw_measure_spec* spec, tw_measure_out* total, uint64_t* hist, tw_measure_out* per,
-               double* kernel_ms) {
+int sh_measure(tw_shard* c, const tw_measure_spec* spec, const MeasureCfg& cfg, tw_measure_out* total, uint64_t* hist,
+               tw_measure_out* per, double* kernel_ms, double* phase_ms) {
     int rc = sh_measure_state(c);
     if (rc) return rc;
     const Dev& d = c->d;
     if (c->lpb)  // (one count per replica in trace_n; d.R counts lanes)
-        return measure_run(c->device, c->stream, d.trace, d.trace_n, c->n_rep, d.trace_cap, spec, total, hist, per,
-                           kernel_ms);
-    return measure_run(c->device, c->stream, d.trace, d.scal + (size_t)SC_TRACE_N * d.R, d.R, d.trace_cap, spec,
-                       total, hist, per, kernel_ms);
+        return measure_run(c->device, c->stream, d.trace, d.trace_n, c->n_rep, d.trace_cap, spec, cfg, total, hist, per,
+                           kernel_ms, phase_ms);
+    return measure_run(c->device, c->stream, d.trace, d.scal + (size_t)SC_TRACE_N * d.R, d.R, d.trace_cap, spec, cfg,
+                       total, hist, per, kernel_ms, phase_ms);
 }
 
 int sh_last_launch_ms(tw_shard* c, double* out, size_t cap) {

@@ -26,6 +26,36 @@
 //     workgroup, one global atomic per non-empty bin and per total.
 // Everything is integer, so the order of the atomics cannot change a result.
 //
+// Replicas with more than TW_MEASURE_MAX_KEYS matching records (accepted once
+// tw_set_measure_keys raised the limit) take the partition path behind it: no
+// sort, since a class needs only "once / more than once" per side and
+// t_to - t_from.  Its kernels, stream-ordered:
+//   tw_measure_plan        one lane per replica over cnt[R]: the large
+//     replicas, their bucket counts (measure_part.hpp) and bucket bases,
+//     claimed with atomics, the totals the host sizes the scratch from, and the
+//     "over the limit" flag; large replicas get cnt[r] = MAX_KEYS + 1, which
+//     tw_measure_join skips, leaving per[r] as the identity;
+//   tw_measure_part<false> counts the keys per (replica, bucket, side);
+//   tw_measure_ranges      every bucket claims its key range with one atomicAdd;
+//   tw_measure_part<true>  scatters (val, t) into the ranges, tag_from keys
+//     from a range's front and tag_to keys behind them: 16 B per key, the side
+//     is the position.  Both part kernels give a workgroup a tile of T
+//     neighbouring replicas x a chunk of n, T the largest power of two with
+//     T x 2 x buckets <= 8192 LDS counters: a wave reads T x 32 contiguous
+//     bytes per n of the [n][R][2] layout, and global atomics are one per
+//     non-empty (replica, bucket, side) of the workgroup, not one per key;
+//   tw_measure_join_large  a fixed grid, each workgroup a contiguous run of
+//     buckets: per bucket an open-addressed LDS table of 2048 slots (val, acc,
+//     state), insert by 64-bit compare-and-swap against the empty mark (the id
+//     equal to the mark has a slot of its own), sticky once / more bits per
+//     side, acc += side ? t : -t; a sweep classifies the slots into the
+//     replica's accumulators (flushed with global atomics when the replica
+//     changes: a replica's buckets may span workgroups) and the workgroup's
+//     histogram.  More than 2048 distinct ids in one bucket raise a flag; the
+//     call then returns TW_ERR_INVALID with nothing written.
+// No lane waits for another, every probe loop ends after 2048 steps, every
+// barrier is under a workgroup-uniform condition.
+//
 // LDS per workgroup: 2048 keys x (8 B val + 8 B t + 1 B flags) = 34 KiB, the
 // histogram 4096 x 4 B = 16 KiB, a few accumulators: ~50.1 KiB static, under
 // the 64 KiB a workgroup may hold; 3 workgroups per CU of the 160 KiB.
@@ -33,11 +63,11 @@
 // Out of scope: TRACE records of node-partitioned contexts (tw_lp_load:
 // tw_set_trace refuses them -- one replica's nodes spread over contexts),
 // records of tw_lp_batch (a traced LPB run keeps its due records on the
-// lanes' chains instead), replicas with more than TW_MEASURE_MAX_KEYS
-// matching records (no global-memory sort path), a job-wide reduction over
-// ranks.
+// lanes' chains instead), a job-wide reduction over ranks, chunking the
+// partition path's scratch over several passes.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <climits>
 #include <cstdint>
 #include <cstdio>
@@ -45,6 +75,7 @@
 
 #include "../../include/timewarp.h"
 #include "measure_combine.hpp"
+#include "measure_part.hpp"
 #include "shard.hpp"
 
 namespace {
@@ -248,12 +279,313 @@ __global__ __launch_bounds__(MS_WG) void tw_measure_join(const uint4* __restrict
     }
 }
 
+// ---------------------------------------------------------- partition path
+using tw::MP_EMPTY;
+using tw::MP_SLOTS;
+
+constexpr uint32_t ML_NONE = 0xFFFFFFFFu;   // MsRep::log2b of a replica the partition path skips
+constexpr uint32_t ML_CTRS = 8192;          // LDS counters of a part workgroup: [replica of the tile][bucket][side]
+constexpr uint32_t ML_TILE_MAX = 64;        // replicas per tile at most: a wave's lanes
+constexpr uint32_t ML_WG_RECORDS = 65536;   // records (tile x chunk) one part workgroup scans
+constexpr uint32_t ML_GRID = 512;           // tw_measure_join_large: 256 CUs x 2 workgroups
+constexpr uint32_t ML_OVER = 1, ML_TABLE = 2;  // MsPlan::flags
+static_assert(ML_CTRS == 2u << tw::MP_MAX_LOG2B, "one replica's buckets x 2 sides fit the counters at T = 1");
+static_assert(MP_SLOTS * 20 + 20 + MS_BINS * 4 + 256 <= 64 * 1024, "static LDS of tw_measure_join_large");
+
+struct MsRep {       // what the partition path knows of replica r
+    uint32_t kept;   // records to scan
+    uint32_t log2b;  // log2 of its bucket count, ML_NONE: not large (or truncated)
+    uint32_t bbase;  // its first bucket among all
+    uint32_t m;      // its matching records
+    unsigned long long kbase;  // its first key among all
+};
+struct MsPlan {  // read by the host after tw_measure_plan (ML_TABLE: after the join)
+    uint32_t flags, n_large, max_log2b, max_kept;
+    unsigned long long n_buckets, n_keys;
+};
+
+__global__ __launch_bounds__(MS_WG) void tw_measure_plan(const uint64_t* __restrict__ emitted, uint32_t R,
+                                                         uint32_t lds_keys, uint32_t max_keys, uint32_t bucket_keys,
+                                                         uint32_t* __restrict__ cnt, MsRep* __restrict__ rep,
+                                                         uint32_t* __restrict__ large, MsPlan* plan) {
+    const uint32_t r = blockIdx.x * MS_WG + threadIdx.x;
+    if (r >= R) return;
+    const uint32_t m = cnt[r];
+    MsRep o{0, ML_NONE, 0, 0, 0};
+    if (m != MS_TRUNC && m > lds_keys) {
+        if (m > max_keys) {
+            atomicOr(&plan->flags, ML_OVER);
+        } else {
+            o.kept = (uint32_t)emitted[r];  // (not truncated: emitted <= cap)
+            o.log2b = tw::mp_log2_buckets(m, bucket_keys);
+            o.bbase = (uint32_t)atomicAdd(&plan->n_buckets, 1ull << o.log2b);
+            o.m = m;
+            o.kbase = atomicAdd(&plan->n_keys, (unsigned long long)m);
+            atomicMax(&plan->max_log2b, o.log2b);
+            atomicMax(&plan->max_kept, o.kept);
+            large[atomicAdd(&plan->n_large, 1u)] = r;
+            cnt[r] = MS_KEYS + 1;  // tw_measure_join: skip, per[r] = the identity
+        }
+    }
+    rep[r] = o;
+}
+
+// A workgroup scans replicas r0 .. r0 + T - 1 (T = 1 << tlog2) over n0 ..
+// n0 + chunk - 1: lane (n, r) -> tid = n * T + (r - r0).  blog2 is the batch's
+// largest log2b: counter [(r - r0) << blog2 | bucket][side].
+template <bool SCATTER>
+__global__ __launch_bounds__(MS_WG) void tw_measure_part(const uint4* __restrict__ trace, uint32_t R, uint32_t tag_from,
+                                                         uint32_t tag_to, const MsRep* __restrict__ rep,
+                                                         uint32_t tlog2, uint32_t blog2, uint32_t chunk,
+                                                         uint32_t tiles, unsigned long long n_buckets,
+                                                         unsigned long long n_keys, uint32_t* __restrict__ bcnt,
+                                                         uint32_t* __restrict__ fill, uint4* __restrict__ keys) {
+    __shared__ uint32_t s_c[ML_CTRS];  // counts; in the scatter then each counter's claimed offset, the local cursor
+    const uint32_t tid = threadIdx.x;
+    const uint32_t T = 1u << tlog2, used = 2u << (tlog2 + blog2);  // <= ML_CTRS (the host chose tlog2 so)
+    const uint32_t r0 = (blockIdx.x % tiles) << tlog2, n0 = (blockIdx.x / tiles) * chunk;
+    const uint32_t dr = tid & (T - 1), r = r0 + dr;
+    MsRep me{0, ML_NONE, 0, 0, 0};
+    if (r < R) me = rep[r];
+    const bool mine = me.log2b != ML_NONE;
+    const uint32_t n_end = mine ? (me.kept < n0 + chunk ? me.kept : n0 + chunk) : 0u;
+    const uint32_t n_step = MS_WG >> tlog2;
+
+    for (uint32_t i = tid; i < used; i += MS_WG) s_c[i] = 0;
+    __syncthreads();
+    for (uint32_t n = n0 + (tid >> tlog2); n < n_end; n += n_step) {
+        const uint4* q = trace + ((size_t)n * R + r) * 2;
+        const uint4 a = q[0];
+        if (a.w == tag_from || a.w == tag_to) {
+            const uint4 b = q[1];
+            const uint32_t bk = tw::mp_bucket_of((int64_t)(((uint64_t)b.y << 32) | b.x), me.log2b);
+            atomicAdd(&s_c[(((dr << blog2) | bk) << 1) | (a.w == tag_to ? 1u : 0u)], 1u);
+        }
+    }
+    __syncthreads();
+    // one global atomic per non-empty counter (a non-empty counter belongs to
+    // a large replica and to one of its buckets)
+    for (uint32_t i = tid; i < used; i += MS_WG) {
+        const uint32_t c = s_c[i];
+        if (!c) continue;
+        const MsRep o = rep[r0 + (i >> (blog2 + 1))];
+        const unsigned long long gb = (unsigned long long)o.bbase + ((i >> 1) & ((1u << blog2) - 1));
+        if (gb >= n_buckets) continue;
+        if (!SCATTER) {
+            atomicAdd(&bcnt[2 * gb + (i & 1)], c);
+        } else {
+            s_c[i] = atomicAdd(&fill[2 * gb + (i & 1)], c);
+        }
+    }
+    if (!SCATTER) return;
+    __syncthreads();
+    for (uint32_t n = n0 + (tid >> tlog2); n < n_end; n += n_step) {
+        const uint4* q = trace + ((size_t)n * R + r) * 2;
+        const uint4 a = q[0];
+        if (a.w == tag_from || a.w == tag_to) {
+            const uint4 b = q[1];
+            const uint32_t bk = tw::mp_bucket_of((int64_t)(((uint64_t)b.y << 32) | b.x), me.log2b);
+            const uint32_t i = (((dr << blog2) | bk) << 1) | (a.w == tag_to ? 1u : 0u);
+            const uint32_t off = atomicAdd(&s_c[i], 1u);  // within the replica's keys
+            const unsigned long long at = me.kbase + off;
+            if (off < me.m && at < n_keys) keys[at] = make_uint4(b.x, b.y, a.x, a.y);  // (val, t)
+        }
+    }
+}
+
+// one workgroup per large replica: each of its buckets claims its key range
+// within the replica's (offsets from MsRep::kbase)
+__global__ __launch_bounds__(MS_WG) void tw_measure_ranges(const uint32_t* __restrict__ large,
+                                                           const MsRep* __restrict__ rep,
+                                                           const uint32_t* __restrict__ bcnt,
+                                                           unsigned long long n_buckets,
+                                                           uint32_t* __restrict__ bstart, uint32_t* __restrict__ brep,
+                                                           uint32_t* __restrict__ fill) {
+    __shared__ uint32_t s_cur;
+    const uint32_t r = large[blockIdx.x];
+    const MsRep o = rep[r];
+    if (threadIdx.x == 0) s_cur = 0;
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < (1u << o.log2b); b += MS_WG) {
+        const unsigned long long gb = (unsigned long long)o.bbase + b;
+        if (gb >= n_buckets) continue;
+        const uint32_t cf = bcnt[2 * gb], ct = bcnt[2 * gb + 1];
+        const uint32_t at = atomicAdd(&s_cur, cf + ct);  // (the counts of a replica sum to its m)
+        bstart[gb] = at;
+        brep[gb] = r;
+        fill[2 * gb] = at;
+        fill[2 * gb + 1] = at + cf;
+    }
+}
+
+// slot state: a side's "seen" bit, and its "seen again" bit
+constexpr uint32_t SF_FROM = 1, SF_FROM2 = 2, SF_TO = 4, SF_TO2 = 8;
+
+__global__ __launch_bounds__(MS_WG) void tw_measure_join_large(const uint4* __restrict__ keys,
+                                                               const uint32_t* __restrict__ bcnt,
+                                                               const uint32_t* __restrict__ bstart,
+                                                               const uint32_t* __restrict__ brep,
+                                                               const MsRep* __restrict__ rep,
+                                                               uint32_t n_buckets, uint32_t per_wg,
+                                                               unsigned long long n_keys, uint32_t n_bins,
+                                                               int64_t lo_us, int64_t bin_us, MsPlan* plan,
+                                                               tw_measure_out* total, unsigned long long* hist,
+                                                               tw_measure_out* per) {
+    // slot MP_SLOTS is the id MP_EMPTY's own
+    __shared__ unsigned long long s_val[MP_SLOTS + 1];
+    __shared__ unsigned long long s_acc[MP_SLOTS + 1];
+    __shared__ uint32_t s_st[MP_SLOTS + 1];
+    __shared__ uint32_t s_hist[MS_BINS];
+    __shared__ uint32_t s_cls[4];  // the current replica's pairs, open_from, open_to, repeated (of this workgroup's buckets)
+    __shared__ long long s_min, s_max;
+    __shared__ unsigned long long s_sum;
+    __shared__ unsigned long long s_uf, s_of;
+    __shared__ uint32_t s_full;
+    const uint32_t tid = threadIdx.x;
+
+    for (uint32_t b = tid; b < n_bins; b += MS_WG) s_hist[b] = 0;
+    if (tid == 0) {
+        s_uf = s_of = 0;
+        s_full = 0;
+        s_cls[0] = s_cls[1] = s_cls[2] = s_cls[3] = 0;
+        s_min = INT64_MAX;
+        s_max = INT64_MIN;
+        s_sum = 0;
+    }
+    tw_measure_out wg;  // the workgroup's totals (thread 0)
+    wg.pairs = wg.open_from = wg.open_to = wg.repeated = 0;
+    wg.min_us = INT64_MAX;
+    wg.max_us = INT64_MIN;
+    wg.sum_us = 0;
+    // thread 0: the replica's accumulators into per[r] (other workgroups may
+    // hold more of its buckets: atomics onto the identity tw_measure_join
+    // wrote) and into the workgroup's totals; then reset
+    auto flush = [&](uint32_t r) {
+        const uint64_t np = s_cls[0];
+        if (per) {
+            tw_measure_out* o = per + r;
+            if (np) atomicAdd((unsigned long long*)&o->pairs, (unsigned long long)np);
+            if (s_cls[1]) atomicAdd((unsigned long long*)&o->open_from, (unsigned long long)s_cls[1]);
+            if (s_cls[2]) atomicAdd((unsigned long long*)&o->open_to, (unsigned long long)s_cls[2]);
+            if (s_cls[3]) atomicAdd((unsigned long long*)&o->repeated, (unsigned long long)s_cls[3]);
+            if (np) {
+                atomicAdd((unsigned long long*)&o->sum_us, s_sum);
+                __hip_atomic_fetch_min((long long*)&o->min_us, s_min, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_max((long long*)&o->max_us, s_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        wg.pairs += np; wg.open_from += s_cls[1]; wg.open_to += s_cls[2]; wg.repeated += s_cls[3];
+        wg.min_us = s_min < wg.min_us ? s_min : wg.min_us;
+        wg.max_us = s_max > wg.max_us ? s_max : wg.max_us;
+        wg.sum_us = (int64_t)((uint64_t)wg.sum_us + s_sum);
+        s_cls[0] = s_cls[1] = s_cls[2] = s_cls[3] = 0;
+        s_min = INT64_MAX;
+        s_max = INT64_MIN;
+        s_sum = 0;
+    };
+
+    // gb, the bucket's counts and its replica depend on the workgroup alone:
+    // every branch that holds a barrier below is taken by all of it or none
+    const uint32_t g0 = blockIdx.x * per_wg < n_buckets ? blockIdx.x * per_wg : n_buckets;
+    const uint32_t g1 = n_buckets - g0 < per_wg ? n_buckets : g0 + per_wg;
+    uint32_t cur = ML_NONE;
+    for (uint32_t gb = g0; gb < g1; ++gb) {
+        const uint32_t cf = bcnt[2 * gb], ct = bcnt[2 * gb + 1], m = cf + ct;
+        if (m == 0) continue;
+        const uint32_t r = brep[gb];
+        const unsigned long long at = rep[r].kbase + bstart[gb];
+        if (at + m > n_keys) continue;
+        if (r != cur) {
+            // (the sweep's closing barrier is behind us: the accumulators are final)
+            if (tid == 0 && cur != ML_NONE) flush(cur);
+            cur = r;
+        }
+        for (uint32_t s = tid; s <= MP_SLOTS; s += MS_WG) {
+            s_val[s] = (unsigned long long)MP_EMPTY;
+            s_acc[s] = 0;
+            s_st[s] = 0;
+        }
+        __syncthreads();
+        for (uint32_t i = tid; i < m; i += MS_WG) {
+            const uint4 k = keys[at + i];
+            const unsigned long long v = ((unsigned long long)k.y << 32) | k.x;
+            const unsigned long long t = ((unsigned long long)k.w << 32) | k.z;
+            const bool to = i >= cf;
+            uint32_t s = MP_SLOTS;
+            if (v != (unsigned long long)MP_EMPTY) {
+                s = tw::mp_slot_of((int64_t)v);
+                uint32_t probes = 0;
+                for (; probes < MP_SLOTS; ++probes) {
+                    const unsigned long long old = atomicCAS(&s_val[s], (unsigned long long)MP_EMPTY, v);
+                    if (old == (unsigned long long)MP_EMPTY || old == v) break;
+                    s = (s + 1) & (MP_SLOTS - 1);
+                }
+                if (probes == MP_SLOTS) {  // more than MP_SLOTS distinct ids in this bucket
+                    s_full = 1;
+                    continue;
+                }
+            }
+            const uint32_t once = to ? SF_TO : SF_FROM;
+            if (atomicOr(&s_st[s], once) & once) atomicOr(&s_st[s], once << 1);
+            atomicAdd(&s_acc[s], to ? t : 0ull - t);
+        }
+        __syncthreads();
+        for (uint32_t s = tid; s <= MP_SLOTS; s += MS_WG) {
+            const uint32_t st = s_st[s];
+            if (!st) continue;
+            uint32_t cls;  // 0 pair, 1 open_from, 2 open_to, 3 repeated
+            if (st & (SF_FROM2 | SF_TO2)) cls = 3u;
+            else if (st == (SF_FROM | SF_TO)) cls = 0u;
+            else cls = st == SF_FROM ? 1u : 2u;
+            atomicAdd(&s_cls[cls], 1u);
+            if (cls == 0) {
+                const int64_t d = (int64_t)s_acc[s];
+                __hip_atomic_fetch_min(&s_min, (long long)d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_max(&s_max, (long long)d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                atomicAdd(&s_sum, (unsigned long long)d);
+                if (d < lo_us) {
+                    atomicAdd(&s_uf, 1ull);
+                } else {
+                    const uint64_t bin = ((uint64_t)d - (uint64_t)lo_us) / (uint64_t)bin_us;
+                    if (bin >= n_bins) atomicAdd(&s_of, 1ull);
+                    else atomicAdd(&s_hist[(uint32_t)bin], 1u);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+    for (uint32_t b = tid; b < n_bins; b += MS_WG)
+        if (s_hist[b]) atomicAdd(&hist[b], (unsigned long long)s_hist[b]);
+    if (tid == 0) {
+        if (cur != ML_NONE) flush(cur);
+        if (s_full) atomicOr(&plan->flags, ML_TABLE);
+        auto add = [](uint64_t* p, uint64_t v) {
+            if (v) atomicAdd((unsigned long long*)p, (unsigned long long)v);
+        };
+        add(&total->pairs, wg.pairs); add(&total->open_from, wg.open_from); add(&total->open_to, wg.open_to);
+        add(&total->repeated, wg.repeated);
+        add(&total->underflow, s_uf); add(&total->overflow, s_of);
+        add((uint64_t*)&total->sum_us, (uint64_t)wg.sum_us);
+        if (wg.pairs) {
+            __hip_atomic_fetch_min((long long*)&total->min_us, (long long)wg.min_us, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_max((long long*)&total->max_us, (long long)wg.max_us, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
 // the call's device scratch and events, released on every return path
 struct MsRes {
     void* buf = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    void* plan = nullptr;  // partition path: header, per-replica entries, the large list
+    void* part = nullptr;  // partition path: per-bucket arrays and the keys
+    hipEvent_t ev[11] = {};  // 0-3: the LDS path's; 4-10: made when the partition path runs
     ~MsRes() {
         if (buf) (void)hipFree(buf);
+        if (plan) (void)hipFree(plan);
+        if (part) (void)hipFree(part);
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
     }
@@ -273,9 +605,12 @@ struct MsRes {
 namespace tw {
 
 int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64_t* emitted, uint32_t R, uint32_t cap,
-                const tw_measure_spec* spec, tw_measure_out* total, uint64_t* hist, tw_measure_out* per,
-                double* kernel_ms) {
+                const tw_measure_spec* spec, const MeasureCfg& cfg, tw_measure_out* total, uint64_t* hist,
+                tw_measure_out* per, double* kernel_ms, double* phase_ms) {
     if (!measure_spec_ok(spec) || !trace || !emitted || cap == 0) return TW_ERR_INVALID;
+    if (cfg.lds_keys > MS_KEYS || cfg.max_keys < MS_KEYS || cfg.max_keys > MP_MAX_KEYS || cfg.bucket_keys == 0)
+        return TW_ERR_INVALID;
+    if (phase_ms) std::fill(phase_ms, phase_ms + MEASURE_PHASES, 0.0);
     if (R == 0) {
         if (total) measure_empty(total);
         if (hist) std::memset(hist, 0, (size_t)spec->n_bins * 8);
@@ -290,7 +625,7 @@ int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64
     MsRes res;
     MSCHK(hipSetDevice(device));
     MSCHK(hipMalloc(&res.buf, bytes));
-    for (hipEvent_t& e : res.ev) MSCHK(hipEventCreate(&e));
+    for (int i = 0; i < 4; ++i) MSCHK(hipEventCreate(&res.ev[i]));
     char* base = (char*)res.buf;
     uint32_t* d_err = (uint32_t*)base;
     tw_measure_out* d_total = (tw_measure_out*)(base + o_total);
@@ -307,7 +642,89 @@ int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64
     uint32_t h_err = 0;
     MSCHK(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, stream));
     MSCHK(hipStreamSynchronize(stream));
-    if (h_err) return TW_ERR_INVALID;  // some replica holds more keys than the join can sort
+    // some replica holds more keys than the LDS join sorts: the partition
+    // path's business when the limit was raised (under the testing hook the
+    // plan decides, whatever the error word says)
+    const bool plan_needed = h_err ? cfg.max_keys > MS_KEYS : cfg.lds_keys < MS_KEYS;
+    if (h_err && !plan_needed) return TW_ERR_INVALID;
+    MsPlan plan{};
+    MsRep* d_rep = nullptr;
+    uint32_t *d_large = nullptr, *d_bcnt = nullptr, *d_bstart = nullptr, *d_brep = nullptr;
+    uint4* d_keys = nullptr;
+    if (plan_needed) {
+        // plan scratch: header (64 B) | rep[R] | large[R]
+        const size_t o_rep = 64, o_large = o_rep + (size_t)R * sizeof(MsRep);
+        static_assert(sizeof(MsPlan) <= 64 && sizeof(MsRep) == 24, "the scratch formula of measure_part.hpp");
+        if (hipMalloc(&res.plan, o_large + (size_t)R * 4) != hipSuccess) {
+            (void)hipGetLastError();  // (not sticky: the context stays usable)
+            return TW_ERR_OOM;
+        }
+        for (int i = 4; i < 11; ++i) MSCHK(hipEventCreate(&res.ev[i]));
+        MsPlan* d_plan = (MsPlan*)res.plan;
+        d_rep = (MsRep*)((char*)res.plan + o_rep);
+        d_large = (uint32_t*)((char*)res.plan + o_large);
+        MSCHK(hipMemsetAsync(d_plan, 0, 64, stream));
+        MSCHK(hipEventRecord(res.ev[4], stream));
+        tw_measure_plan<<<(R + MS_WG - 1) / MS_WG, MS_WG, 0, stream>>>(emitted, R, cfg.lds_keys, cfg.max_keys,
+                                                                      cfg.bucket_keys, d_cnt, d_rep, d_large, d_plan);
+        MSCHK(hipGetLastError());
+        MSCHK(hipEventRecord(res.ev[5], stream));
+        MSCHK(hipMemcpyAsync(&plan, d_plan, sizeof plan, hipMemcpyDeviceToHost, stream));
+        MSCHK(hipStreamSynchronize(stream));
+        // over the limit: decided before the key scratch exists.  Everything
+        // below is bounded by these words: n_large <= R, max_log2b <=
+        // MP_MAX_LOG2B, n_keys <= R * max_keys, bucket indices in 32 bits
+        if (plan.flags & ML_OVER) return TW_ERR_INVALID;
+        if (plan.n_large > R || plan.max_log2b > MP_MAX_LOG2B || plan.max_kept > cap ||
+            plan.n_buckets > 0x7FFFFFFFull || plan.n_keys > (unsigned long long)R * cfg.max_keys)
+            return TW_ERR_STATE;
+    }
+    if (plan.n_large) {
+        // part scratch: bcnt[2 B] | fill[2 B] | bstart[B] | brep[B] | keys[K] (16 B each, 16-aligned)
+        const size_t B = (size_t)plan.n_buckets, K = (size_t)plan.n_keys;
+        const size_t o_fill = B * 8, o_bstart = o_fill + B * 8, o_brep = o_bstart + B * 4;
+        const size_t o_keys = (o_brep + B * 4 + 15) & ~(size_t)15;
+        if (hipMalloc(&res.part, o_keys + K * 16) != hipSuccess) {
+            (void)hipGetLastError();
+            return TW_ERR_OOM;
+        }
+        char* pb = (char*)res.part;
+        d_bcnt = (uint32_t*)pb;
+        uint32_t* d_fill = (uint32_t*)(pb + o_fill);
+        d_bstart = (uint32_t*)(pb + o_bstart);
+        d_brep = (uint32_t*)(pb + o_brep);
+        d_keys = (uint4*)(pb + o_keys);
+        // a tile of T replicas x their buckets x 2 sides within the LDS
+        // counters; a workgroup scans about ML_WG_RECORDS records
+        uint32_t tlog2 = MP_MAX_LOG2B - plan.max_log2b;
+        if (tlog2 > 6) tlog2 = 6;  // ML_TILE_MAX
+        while (tlog2 > 0 && (1u << (tlog2 - 1)) >= R) --tlog2;
+        static_assert(ML_TILE_MAX == 64 && (2u << MP_MAX_LOG2B) == ML_CTRS, "tile size against the counters");
+        const uint32_t tiles = (uint32_t)(((uint64_t)R + (1u << tlog2) - 1) >> tlog2);
+        uint32_t chunk = ML_WG_RECORDS >> tlog2;
+        uint64_t chunks = ((uint64_t)plan.max_kept + chunk - 1) / chunk;
+        while ((uint64_t)tiles * chunks > 0x7FFFFFFFull) {  // (the grid's limit; never at sizes memory holds)
+            chunk *= 2;
+            chunks = ((uint64_t)plan.max_kept + chunk - 1) / chunk;
+        }
+        const uint32_t pgrid = (uint32_t)((uint64_t)tiles * (chunks ? chunks : 1));
+        MSCHK(hipEventRecord(res.ev[6], stream));
+        MSCHK(hipMemsetAsync(d_bcnt, 0, B * 8, stream));
+        tw_measure_part<false><<<pgrid, MS_WG, 0, stream>>>(trace, R, spec->tag_from, spec->tag_to, d_rep, tlog2,
+                                                            plan.max_log2b, chunk, tiles, plan.n_buckets, plan.n_keys,
+                                                            d_bcnt, d_fill, d_keys);
+        MSCHK(hipGetLastError());
+        MSCHK(hipEventRecord(res.ev[7], stream));
+        tw_measure_ranges<<<plan.n_large, MS_WG, 0, stream>>>(d_large, d_rep, d_bcnt, plan.n_buckets, d_bstart, d_brep,
+                                                              d_fill);
+        MSCHK(hipGetLastError());
+        MSCHK(hipEventRecord(res.ev[8], stream));
+        tw_measure_part<true><<<pgrid, MS_WG, 0, stream>>>(trace, R, spec->tag_from, spec->tag_to, d_rep, tlog2,
+                                                           plan.max_log2b, chunk, tiles, plan.n_buckets, plan.n_keys,
+                                                           d_bcnt, d_fill, d_keys);
+        MSCHK(hipGetLastError());
+        MSCHK(hipEventRecord(res.ev[9], stream));
+    }
 
     // a workgroup's histogram counters are 32-bit: at most 2^20 replicas of
     // <= MS_KEYS / 2 pairs each per workgroup
@@ -319,6 +736,22 @@ int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64
                                                 spec->lo_us, spec->bin_us, d_cnt, d_total, d_hist, d_per);
     MSCHK(hipGetLastError());
     MSCHK(hipEventRecord(res.ev[3], stream));
+    if (plan.n_large) {
+        // behind tw_measure_join, which wrote the large replicas' per[r] as the
+        // identity.  32-bit histogram counters: at most 2^20 buckets of <=
+        // MP_SLOTS + 1 pairs each per workgroup
+        const uint32_t B = (uint32_t)plan.n_buckets;
+        uint32_t lgrid = B < ML_GRID ? B : ML_GRID;
+        const uint32_t lneed = (uint32_t)(((uint64_t)B + (1u << 20) - 1) >> 20);
+        if (lgrid < lneed) lgrid = lneed;
+        const uint32_t per_wg = (B + lgrid - 1) / lgrid;
+        tw_measure_join_large<<<lgrid, MS_WG, 0, stream>>>(d_keys, d_bcnt, d_bstart, d_brep, d_rep, B, per_wg,
+                                                           plan.n_keys, spec->n_bins, spec->lo_us, spec->bin_us,
+                                                           (MsPlan*)res.plan, d_total, d_hist, d_per);
+        MSCHK(hipGetLastError());
+        MSCHK(hipEventRecord(res.ev[10], stream));
+        MSCHK(hipMemcpyAsync(&plan.flags, res.plan, 4, hipMemcpyDeviceToHost, stream));
+    }
     // host copies of the device results: the caller's buffers are written
     // only once everything has succeeded
     std::vector<char> h_head(o_per - o_total);
@@ -326,13 +759,29 @@ int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64
     MSCHK(hipMemcpyAsync(h_head.data(), base + o_total, h_head.size(), hipMemcpyDeviceToHost, stream));
     if (per) MSCHK(hipMemcpyAsync(h_per.data(), d_per, (size_t)R * sizeof(tw_measure_out), hipMemcpyDeviceToHost, stream));
     MSCHK(hipStreamSynchronize(stream));
+    if (plan.flags & ML_TABLE) return TW_ERR_INVALID;  // a bucket held more distinct ids than its table
     float ms_a = 0.f, ms_b = 0.f;
     MSCHK(hipEventElapsedTime(&ms_a, res.ev[0], res.ev[1]));
     MSCHK(hipEventElapsedTime(&ms_b, res.ev[2], res.ev[3]));
+    // count, plan, part<false>, ranges, part<true>, join, join_large
+    double ph[MEASURE_PHASES] = {ms_a, 0, 0, 0, 0, ms_b, 0};
+    if (plan_needed) {
+        static const int span[MEASURE_PHASES][2] = {{0, 1}, {4, 5}, {6, 7}, {7, 8}, {8, 9}, {2, 3}, {3, 10}};
+        for (int i = 1; i < MEASURE_PHASES; ++i) {
+            if (i == 5 || (i > 1 && !plan.n_large)) continue;
+            float ms = 0.f;
+            MSCHK(hipEventElapsedTime(&ms, res.ev[span[i][0]], res.ev[span[i][1]]));
+            ph[i] = ms;
+        }
+    }
     if (total) std::memcpy(total, h_head.data(), sizeof(tw_measure_out));
     if (hist) std::memcpy(hist, h_head.data() + sizeof(tw_measure_out), (size_t)spec->n_bins * 8);
     if (per) std::memcpy(per, h_per.data(), (size_t)R * sizeof(tw_measure_out));
-    if (kernel_ms) *kernel_ms = (double)ms_a + (double)ms_b;
+    if (kernel_ms) {
+        *kernel_ms = 0.0;
+        for (double v : ph) *kernel_ms += v;
+    }
+    if (phase_ms) std::copy(ph, ph + MEASURE_PHASES, phase_ms);
     return TW_OK;
 }
 

@@ -47,15 +47,25 @@ TW_HIDDEN int sh_read_trace(tw_shard* c, uint32_t replica, tw_trace_rec* out, si
 // (TW_ERR_STATE nothing loaded / tracing off, TW_ERR_INVALID node-partitioned
 // contexts and batched LP contexts with tracing off);
 // sh_measure writes total, hist[n_bins] (or NULL), per[sh_replicas] (or NULL)
-// and the kernels' device time only on success
+// and the kernels' device time (phase_ms: MEASURE_PHASES entries or NULL)
+// only on success.  MeasureCfg is the context's setting (tw_set_measure_keys)
+// with the testing hook's two values (TW_TEST_MEASURE; abi.hip)
 TW_HIDDEN int sh_measure_state(tw_shard* c);
-TW_HIDDEN int sh_measure(tw_shard* c, const tw_measure_spec* spec, tw_measure_out* total, uint64_t* hist,
-                         tw_measure_out* per, double* kernel_ms);
+struct MeasureCfg {
+    uint32_t max_keys;     // matching records a non-truncated replica may hold
+    uint32_t lds_keys;     // replicas with more take the partition path (TW_MEASURE_MAX_KEYS but under the hook)
+    uint32_t bucket_keys;  // mean keys per bucket (1024 but under the hook)
+};
+// tw_measure's kernels in launch order of their kind: count, plan,
+// part<false>, ranges, part<true>, join, join_large
+constexpr int MEASURE_PHASES = 7;
+TW_HIDDEN int sh_measure(tw_shard* c, const tw_measure_spec* spec, const MeasureCfg& cfg, tw_measure_out* total,
+                         uint64_t* hist, tw_measure_out* per, double* kernel_ms, double* phase_ms);
 // the measure pass itself (measure.hip) over a shard's trace buffer
 // ([cap][R][2] quads) and its per-replica emitted counts (R: replicas)
 TW_HIDDEN int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64_t* emitted, uint32_t R,
-                          uint32_t cap, const tw_measure_spec* spec, tw_measure_out* total, uint64_t* hist,
-                          tw_measure_out* per, double* kernel_ms);
+                          uint32_t cap, const tw_measure_spec* spec, const MeasureCfg& cfg, tw_measure_out* total,
+                          uint64_t* hist, tw_measure_out* per, double* kernel_ms, double* phase_ms);
 TW_HIDDEN int sh_last_launch_ms(tw_shard* c, double* out, size_t cap);
 TW_HIDDEN int sh_prof_read(tw_shard* c, unsigned long long* out, size_t cap, int reset);
 // shape of what a shard holds: replicas its results cover (batched LP: the

@@ -127,6 +127,7 @@ class TwMeasureOut(C.Structure):
 
 
 MEASURE_MAX_KEYS = 2048   # TW_MEASURE_MAX_KEYS
+MEASURE_MAX_KEYS_LARGE = 4194304   # TW_MEASURE_MAX_KEYS_LARGE (tw_set_measure_keys)
 MEASURE_MAX_BINS = 4096   # TW_MEASURE_MAX_BINS
 
 RESULT_FIELDS = ["final_t", "events", "delivered", "dropped", "undeliverable", "status", "main_exc", "threads"]

@@ -32,7 +32,7 @@ EXPORTS = ["tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_ru
            "tw_set_stream", "tw_lp_exchange_setup", "tw_lp_loop_begin", "tw_lp_tick", "tw_lp_tick_import",
            "tw_lp_tick_end", "tw_lp_progress", "tw_lp_run_windows", "tw_lpb_load", "tw_lpb_windows",
            "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms", "tw_set_sweep", "tw_sweep_stats",
-           "tw_set_prefix", "tw_prefix_stats"]
+           "tw_set_prefix", "tw_prefix_stats", "tw_set_measure_keys", "tw_measure_phases_ms"]
 GEOMETRIES = ("dense", "sparse", "half", "wave", "lp", "narrow", "lpb", "compact")  # TW_GEO_* order
 
 # tw_trace_rec (include/timewarp.h)
@@ -111,6 +111,8 @@ def load_library(path: Optional[str] = None):
     lib.tw_measure.argtypes = [C.c_void_p, C.POINTER(TwMeasureSpec), C.POINTER(TwMeasureOut), C.c_void_p, C.c_void_p,
                                C.c_size_t]
     lib.tw_measure_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.tw_set_measure_keys.argtypes = [C.c_void_p, C.c_uint32]
+    lib.tw_measure_phases_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.tw_set_sweep.argtypes = [C.c_void_p, C.c_int]
     lib.tw_sweep_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
     lib.tw_set_prefix.argtypes = [C.c_void_p, C.c_int]
@@ -122,7 +124,7 @@ def load_library(path: Optional[str] = None):
                  "tw_geometry", "tw_set_stream", "tw_lp_exchange_setup", "tw_lp_loop_begin", "tw_lp_tick",
                  "tw_lp_tick_import", "tw_lp_tick_end", "tw_lp_progress", "tw_lp_run_windows", "tw_lpb_load",
                  "tw_lpb_windows", "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms", "tw_set_sweep",
-                 "tw_sweep_stats", "tw_set_prefix", "tw_prefix_stats"):
+                 "tw_sweep_stats", "tw_set_prefix", "tw_prefix_stats", "tw_set_measure_keys", "tw_measure_phases_ms"):
         getattr(lib, name).restype = C.c_int
     if path is None:
         _lib = lib
@@ -432,6 +434,26 @@ class Engine:
         _check(self.lib.tw_measure(self.ctx, C.byref(spec), C.byref(tot), hist.ctypes.data if hist.size else None,
                                    per.ctypes.data if n else None, n), "tw_measure")
         return {f: int(getattr(tot, f)) for f, _ in TwMeasureOut._fields_}, hist, per
+
+    def set_measure_keys(self, max_keys: int) -> "Engine":
+        """The matching records one non-truncated replica may hold in measure()
+        (tw_set_measure_keys): MEASURE_MAX_KEYS, the default, up to
+        MEASURE_MAX_KEYS_LARGE.  Above the default, replicas too large for the
+        LDS join are hash-partitioned through device scratch allocated per
+        call.  Kept across load, reset and set_trace."""
+        v = int(max_keys)
+        _check(self.lib.tw_set_measure_keys(self.ctx, v if 0 <= v < 1 << 32 else 0), "tw_set_measure_keys")
+        return self
+
+    MEASURE_PHASES = ("count", "plan", "part_count", "ranges", "part_scatter", "join", "join_large")
+
+    def measure_phases_ms(self) -> dict:
+        """Device time (ms) of the last measure() by kernel (the slowest
+        shard's; 0 for kernels that did not run)."""
+        buf = np.zeros(len(self.MEASURE_PHASES), np.float64)
+        n = self.lib.tw_measure_phases_ms(self.ctx, buf.ctypes.data, buf.shape[0])
+        _check(n, "tw_measure_phases_ms")
+        return dict(zip(self.MEASURE_PHASES[:n], buf[:n].tolist()))
 
     def measure_ms(self) -> float:
         """Device time (ms) of the last measure()'s kernels."""

@@ -11,8 +11,16 @@ the node's chain (tw_lp_batch is off while tracing is on), and Engine.trace
 returns a replica's records in canonical order, so the host sample is compared
 as sorted tuples.
 
+--max-keys N raises the context's key limit (Engine.set_measure_keys): replicas
+with more than 2,048 keys of the round trip (senders x messages > 1,024) then
+take the partition path, and every call's line is followed by the kernels' time
+by phase with the bytes each phase moves by design (records scanned x 32 B, keys
+written or read x 16 B; a model, not a counter).  The reference bench's own
+message count: --senders 256 --msgs 1000 --replicas 256 --geometry lpb
+--max-keys 524288 --host-sample 2.
+
 usage: python tools/measure_probe.py [--senders 8] [--msgs 40] [--replicas 65536] [--geometry lpb]
-                                     [--host-sample 256] [--out profiles/measure/probe.log]"""
+                                     [--max-keys N] [--host-sample 256] [--out profiles/measure/probe.log]"""
 import argparse
 import os
 import sys
@@ -32,6 +40,7 @@ ap.add_argument("--senders", type=int, default=8)
 ap.add_argument("--msgs", type=int, default=40)
 ap.add_argument("--replicas", type=int, default=65536)
 ap.add_argument("--host-sample", type=int, default=256)
+ap.add_argument("--max-keys", type=int, default=0, help="Engine.set_measure_keys (default: the library's 2048)")
 ap.add_argument("--geometry", default=None, help="Engine.load's geometry (default: the library's choice)")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "measure", "probe.log"))
 a = ap.parse_args()
@@ -47,9 +56,24 @@ def say(s):
     lines.append(s)
 
 
+def say_phases(e):
+    """The last measure()'s kernels by phase, when the partition path ran."""
+    ph = e.measure_phases_ms()
+    if not ph["join_large"]:
+        return
+    rec, key = cap * R * 32, 2 * S * M * R * 16   # every record is kept; two of a message's four are keys
+    moved = {"count": (rec, 0), "part_count": (rec, 0), "part_scatter": (rec, key), "join_large": (key, 0)}
+    for k, ms in ph.items():
+        rd, wr = moved.get(k, (0, 0))
+        rate = f", reads {rd / 1e9:.2f} GB, writes {wr / 1e9:.2f} GB: {(rd + wr) / ms / 1e6:.0f} GB/s" if rd and ms else ""
+        say(f"    {k:12s} {ms:9.3f} ms{rate}")
+
+
 scn = scenarios.hotspot(n_senders=S, n_replicas=R, msg_num=M, drawer=draw_link_table)
 with Engine(0) as e:
     e.load(scn, geometry=a.geometry)
+    if a.max_keys:
+        e.set_measure_keys(a.max_keys)
     if a.geometry == "lpb":  # what tracing costs there: the same batch untraced, tw_lp_batch on
         e.reset().run()      # (every timed run is a second one: the first loads code and captures the tick graph)
         e.reset()
@@ -72,7 +96,9 @@ with Engine(0) as e:
         total, hist, per = e.measure(spec["tag_from"], spec["tag_to"], spec["lo_us"], spec["bin_us"], spec["n_bins"],
                                      per_replica=True)
         wall = (time.perf_counter() - t0) * 1e3
-        say(f"tw_measure call {i}: wall {wall:.2f} ms, kernels {e.measure_ms():.3f} ms (HIP events)")
+        say(f"tw_measure call {i}: wall {wall:.2f} ms, kernels {e.measure_ms():.3f} ms (HIP events); the rest, "
+            f"{wall - e.measure_ms():.2f} ms, is the call's scratch allocation and release, two host reads and the copy out")
+        say_phases(e)
     t0 = time.perf_counter()
     e.measure(spec["tag_from"], spec["tag_to"], spec["lo_us"], spec["bin_us"], spec["n_bins"])
     say(f"tw_measure without per_replica: wall {(time.perf_counter() - t0) * 1e3:.2f} ms, "
