@@ -564,6 +564,25 @@ int tw_set_prefix(tw_ctx* ctx, int on);
  * Any pointer may be NULL. */
 int tw_prefix_stats(tw_ctx* ctx, int64_t* t0_us, uint64_t* events_per_replica, uint64_t* bytes_per_replica,
                     uint32_t* last_use, double* apply_ms);
+/* Rows an apply leaves unstored.  Most threads of a snapshot stay parked until
+ * a killThread sweep retires them: the kill wakes at the image's last sweep
+ * time and the victims they name (the claimed slots).  That sweep compares
+ * each such thread's tid and queued seq, in every replica, with the
+ * snapshot's; where they are equal the thread's frames and registers were not
+ * written since the last apply, and the next apply after a tw_reset does not
+ * store them again.  Only a tw_run that ends in that sweep with every replica
+ * swept verifies; any call but tw_reset, tw_run and the read-only ones between
+ * it and the next apply makes that apply store every row.  Results are the
+ * same either way.  Of the context's first device: the claimed slots of the
+ * cached snapshot (0: none), the rows the last tw_run's apply skipped and the
+ * bytes it stored per replica (0: no apply), whether the last tw_run verified,
+ * and -- with the testing hook TW_TEST_PREFIX_AUDIT=1 in the environment when
+ * the context was made, which follows every apply that skips rows with a
+ * read-only pass over them -- the elements of skipped rows that differed from
+ * the snapshot's value (always 0 unless the rule above is broken).  Any
+ * pointer may be NULL. */
+int tw_prefix_clean_stats(tw_ctx* ctx, uint32_t* claimed_slots, uint64_t* rows_skipped,
+                          uint64_t* bytes_stored_per_replica, uint32_t* verified, uint64_t* audit_mismatches);
 
 /* Testing hook: from the next tw_reset on, start every replica's insertion
  * counter at seq0 and its thread counter at tid0 (>= 1; main is tid 0), so the

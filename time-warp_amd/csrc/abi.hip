@@ -727,6 +727,13 @@ int tw_prefix_stats(tw_ctx* c, int64_t* t0_us, uint64_t* events_per_replica, uin
     return sh_prefix_stats(c->sh[0], t0_us, events_per_replica, bytes_per_replica, last_use, apply_ms);
 }
 
+int tw_prefix_clean_stats(tw_ctx* c, uint32_t* claimed_slots, uint64_t* rows_skipped, uint64_t* bytes_stored_per_replica,
+                          uint32_t* verified, uint64_t* audit_mismatches) {
+    if (!c || c->sh.empty()) return TW_ERR_INVALID;
+    return sh_prefix_clean_stats(c->sh[0], claimed_slots, rows_skipped, bytes_stored_per_replica, verified,
+                                 audit_mismatches);
+}
+
 int tw_sweep_stats(tw_ctx* c, uint64_t* killers, uint64_t* victims, uint64_t* refused_replicas) {
     if (!c) return TW_ERR_INVALID;
     uint64_t k = 0, v = 0, f = 0;

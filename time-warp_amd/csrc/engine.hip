@@ -294,6 +294,9 @@ int sh_create(int device, tw_shard** out) {
         return TW_ERR_HIP;
     }
     c->own_stream = c->stream;
+    // testing hook: TW_TEST_PREFIX_AUDIT=1 follows every apply that may skip
+    // rows with a read-only kernel over the skipped rows (tw_prefix_clean_stats)
+    if (const char* a = getenv("TW_TEST_PREFIX_AUDIT")) c->px.audit = atoi(a) != 0;
     *out = c;
     return TW_OK;
 }
@@ -771,6 +774,7 @@ static int load_common(tw_shard* c, const tw_scenario_desc* s, bool lp, uint32_t
             c->sw.tab.stats = stats;
             c->sw.tab.near_cap = TW_NEAR_CAP;
             c->sw.times = plan.times;
+            c->sw.stub_h = plan.stub;
         } else {
             (void)hipGetLastError();  // (a failed allocation is not an error of the load)
         }
@@ -867,7 +871,8 @@ static int launch_event(tw_shard* c, hipStream_t st, int64_t t_end, uint64_t lim
 // A sweep time T of the image (Sweep::times[ix]) that lies within the run
 struct Stop { int64_t T; uint32_t ix; };
 // ... and, as the stop ahead of a round: the run's segment it ends, the run's own end
-struct SweepAt { int64_t T, run_end; uint32_t seg; };
+// clean: the kill table is this stop's (Prefix::Snap::Clean) and the replicas derive from its snapshot
+struct SweepAt { int64_t T, run_end; uint32_t seg; bool clean; };
 
 // One round of tw_run: n launches of the event kernel to t_end, each behind a
 // cleared n_active and timed; with a sweep stop ahead, each followed by the
@@ -879,6 +884,7 @@ static int run_round(tw_shard* c, int n, int64_t t_end, uint64_t limit, uint32_t
                      const SweepAt* sw, uint32_t* launches) {
     const Dev& d = c->d;
     hipStream_t st = c->stream;
+    const Prefix::Snap::Clean& cl = c->px.snap.clean;
     for (int i = 0; i < n; ++i) {
         HIPCHK(hipMemsetAsync(d.n_active, 0, 4, st));
         if (c->lp) HIPCHK(hipMemsetAsync(d.next_t, 0xFF, 8, st));
@@ -887,15 +893,71 @@ static int run_round(tw_shard* c, int n, int64_t t_end, uint64_t limit, uint32_t
         ++*launches;
         if (!sw) continue;
         rc = c->times.timed(st, [&]() -> int {
-            HIPCHK(sweep_launch(d, c->sw.tab, st, sw->T, limit, sw->run_end, sw->seg));
+            tw::SweepTab tab = c->sw.tab;
+            if (sw->clean) {
+                tab.kill = cl.kill; tab.kwin = cl.kwin; tab.dirty = cl.dirty; tab.cflags = cl.cflags;
+            }
+            HIPCHK(sweep_launch(d, tab, st, sw->T, limit, sw->run_end, sw->seg));
             return TW_OK;
         }, &c->sw.ms);
         if (rc) return rc;
     }
     HIPCHK(hipMemcpyAsync(c->h_active, d.n_active, 4, hipMemcpyDeviceToHost, st));
     if (sw) HIPCHK(hipMemcpyAsync(c->sw.h, c->sw.tab.stats, 8 * SWS_COUNT, hipMemcpyDeviceToHost, st));
+    // (the dirty bytes and the flag words lie behind one another)
+    if (sw && sw->clean) HIPCHK(hipMemcpyAsync(cl.h, cl.dirty, cl.S + 4 * CF_COUNT, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return c->times.read();
+}
+
+// Rows later applies may skip, for the snapshot just taken: the
+// kill table of the image's last sweep time from the snapshot's own bytes, the
+// claimed slots' row tags, cleared dirty bytes and flag words, in one device
+// block.  Optional: without a sweep time behind the prefix, a claimable
+// position or the memory, every apply stores every row, as before.
+static int build_clean(tw_shard* c, const std::vector<tw::PrefixRow>& rows, const uint64_t* sc) {
+    const Dev& d = c->d;
+    hipStream_t st = c->stream;
+    Prefix::Snap& sn = c->px.snap;
+    if (!c->sw.tab.stub || c->sw.times.empty() || c->sw.stub_h.size() != (size_t)d.n_insns + 1) return TW_OK;
+    const uint32_t stop = (uint32_t)c->sw.times.size() - 1u;
+    const int64_t T = c->sw.times[stop];
+    if (T <= c->px.t0 - 1) return TW_OK;
+    std::vector<uint8_t> snap(sn.bytes);
+    HIPCHK(hipMemcpyAsync(snap.data(), sn.tab.snap, sn.bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const tw::CleanLayout L = tw::clean_layout(d);
+    const tw::CleanPlan plan = tw::clean_build(L, rows.data(), rows.size(), snap.data(), snap.size(), sc + SC_RH0,
+                                               sc + SC_RC0, c->sw.stub_h.data(), T);
+    if (plan.slots.empty()) return TW_OK;
+    const std::vector<uint32_t> tag = tw::clean_tags(L, rows.data(), rows.size(), plan.slots);
+    const size_t S4 = ((size_t)d.S + 3u) & ~(size_t)3u;
+    const size_t o_win = sizeof(tw::KillEnt) * plan.ents.size(), o_tag = o_win + sizeof(tw::KillWin) * TW_RUNS,
+                 o_dirty = o_tag + 4 * tag.size(), o_audit = (o_dirty + S4 + 4 * CF_COUNT + 7u) & ~(size_t)7u,
+                 total = o_audit + 8;
+    Prefix::Snap::Clean& cl = sn.clean;
+    if (hipMalloc(&cl.dev, total) != hipSuccess || hipHostMalloc((void**)&cl.h, S4 + 4 * CF_COUNT) != hipSuccess) {
+        (void)hipGetLastError();  // (no memory: no skipping, not an error of the run)
+        if (cl.dev) (void)hipFree(cl.dev);
+        cl = Prefix::Snap::Clean{};
+        return TW_OK;
+    }
+    uint8_t* b = (uint8_t*)cl.dev;
+    HIPCHK(hipMemset(b, 0, total));
+    HIPCHK(hipMemcpy(b, plan.ents.data(), o_win, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_win, plan.win.data(), sizeof(tw::KillWin) * TW_RUNS, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_tag, tag.data(), 4 * tag.size(), hipMemcpyHostToDevice));
+    std::memset(cl.h, 0, S4 + 4 * CF_COUNT);
+    cl.kill = (const tw::KillEnt*)b;
+    cl.kwin = (const tw::KillWin*)(b + o_win);
+    cl.tag = (const uint32_t*)(b + o_tag);
+    cl.dirty = b + o_dirty;
+    cl.cflags = (uint32_t*)(b + o_dirty + S4);
+    cl.audit = (unsigned long long*)(b + o_audit);
+    cl.S = (uint32_t)S4;
+    cl.stop = stop;
+    cl.slots = plan.slots;
+    return TW_OK;
 }
 
 // The send-free prefix of a fresh run.  With a snapshot cached
@@ -909,7 +971,7 @@ static int run_round(tw_shard* c, int n, int64_t t_end, uint64_t limit, uint32_t
 // pilot that fails the check is remembered as "no prefix" for the key; its
 // replicas are simply ahead of the others and the run goes on as ever.
 // *applied: the apply is on the stream.
-static int run_prefix(tw_shard* c, uint64_t limit, uint32_t budget, uint32_t* launches, bool* applied) {
+static int run_prefix(tw_shard* c, uint64_t limit, uint32_t budget, bool verified, uint32_t* launches, bool* applied) {
     const Dev& d = c->d;
     hipStream_t st = c->stream;
     Prefix& px = c->px;
@@ -961,9 +1023,31 @@ static int run_prefix(tw_shard* c, uint64_t limit, uint32_t budget, uint32_t* la
         px.snap.bytes = bytes;
         HIPCHK(prefix_take(px.snap.tab, st));
         px.snap.ok = true;
+        int rc = build_clean(c, rows, sc);
+        if (rc) return rc;
     }
+    // Rows the last run's sweep proved unwritten are left as they are (§3o):
+    // `skip` is the host's side of the validity rule, CF_VALID the device's.
+    // The flags are consumed: cleared behind the apply, inside its timed pair.
+    const Prefix::Snap::Clean& cl = px.snap.clean;
+    const bool skip = hit && cl.dev && verified;
+    tw::PrefixTab tab = px.snap.tab;
+    px.rows_skipped = 0;
+    if (skip) {
+        tab.tag = cl.tag; tab.dirty = cl.dirty; tab.cflags = cl.cflags;
+        const uint32_t* hf = (const uint32_t*)(cl.h + cl.S);
+        if (hf[CF_VALID])
+            for (uint32_t s : cl.slots) px.rows_skipped += cl.h[s] ? 0u : 3u;
+    }
+    px.bytes_stored = px.snap.bytes - 16u * px.rows_skipped;
     int rc = c->times.timed(st, [&]() -> int {
-        HIPCHK(prefix_apply(px.snap.tab, d.R, px.snap.max_es, st));
+        HIPCHK(prefix_apply(tab, d.R, px.snap.max_es, st));
+        if (skip && px.audit) {
+            HIPCHK(hipMemsetAsync(cl.audit, 0, 8, st));
+            HIPCHK(prefix_audit(tab, d.R, px.snap.max_es, cl.audit, st));
+            px.audited = true;
+        }
+        if (cl.dev) HIPCHK(hipMemsetAsync(cl.dirty, 0, cl.S + 4 * CF_COUNT, st));
         return TW_OK;
     }, &px.ms);
     if (rc) return rc;
@@ -1008,6 +1092,13 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
     c->px.fresh = false;
     c->px.last = TW_PREFIX_NOT_ELIGIBLE;
     c->px.ms = 0.0;
+    // §3o: what the last run verified serves this run's apply alone; the
+    // replicas derive from an apply only if this run, fresh, makes one
+    const bool verified = c->px.verified && was_fresh;
+    c->px.verified = c->px.last_verified = false;
+    if (was_fresh) c->px.chain = false;
+    c->px.rows_skipped = c->px.bytes_stored = 0;
+    c->px.audited = false;
     if (c->lpb) {
         // the batched window loop runs every replica to quiescence
         if (t_end_us != INT64_MAX || max_events != UINT64_MAX) return TW_ERR_INVALID;
@@ -1059,8 +1150,9 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
     if (was_fresh && c->px.on && swept_order && d.trace_cap == 0 && !c->main_regs && c->px.t0 >= 1 &&
         t_end_us >= c->px.t0 - 1) {
         bool applied = false;
-        int rc = run_prefix(c, limit, budget, &launches, &applied);
+        int rc = run_prefix(c, limit, budget, verified, &launches, &applied);
         if (rc) return rc;
+        c->px.chain = applied;
         // (sweep times inside the prefix: the snapshot is past them)
         if (applied)
             for (uint32_t i = 0; i < c->sw.times.size(); ++i)
@@ -1086,11 +1178,14 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
         }
         if (!stops.empty()) HIPCHK(hipMemsetAsync(c->sw.tab.stats, 0, 8 * SWS_COUNT, st));
     }
-    bool quiet = false;
+    bool quiet = false, checked = false;
     size_t seg = 0;
+    const Prefix::Snap::Clean& cl = c->px.snap.clean;
     for (int round = 0; round < (1 << 20) && !quiet; ++round) {
         const bool to_sweep = seg < stops.size();
-        const SweepAt at{to_sweep ? stops[seg].T : 0, t_end_us, (uint32_t)seg};
+        // the kill table's stop, over replicas that derive from its snapshot (§3o)
+        const bool clean = to_sweep && c->px.chain && c->px.snap.ok && cl.dev && stops[seg].ix == cl.stop;
+        const SweepAt at{to_sweep ? stops[seg].T : 0, t_end_us, (uint32_t)seg, clean};
         int rc = run_round(c, per_check, to_sweep ? at.T - 1 : t_end_us, limit, budget, 0, to_sweep ? &at : nullptr,
                            &launches);
         if (rc) return rc;
@@ -1099,6 +1194,7 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
         } else if (c->sw.h[SWS_FIRED] > seg) {
             c->sw.done |= 1u << stops[seg].ix;
             for (int k = 0; k < 3; ++k) c->sw.last[k] = c->sw.h[k];
+            checked = checked || clean;
             ++seg;
             // the last stop swept and no replica has work left before t_end: done
             quiet = seg == stops.size() && c->sw.h[SWS_LEFT] == 0;
@@ -1108,6 +1204,10 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
         int rc = reduce_stats(c, launches, w0, out);
         if (rc) return rc;
     }
+    // the sweep at the table's time fired, checked every replica and left none
+    // with work: the next apply may skip what it did not mark (§3o)
+    if (quiet && checked && ((const uint32_t*)(cl.h + cl.S))[CF_VALID] != 0u)
+        c->px.verified = c->px.last_verified = true;
     return quiet ? TW_OK : TW_ERR_INCOMPLETE;
 }
 
@@ -1174,6 +1274,7 @@ int sh_tie_audit(tw_shard* c, int64_t t_end_us, uint64_t max_events, uint32_t pr
     HIPCHK(hipSetDevice(c->device));
     std::vector<std::vector<uint64_t>> dg(probes + 1);
     int rc = TW_OK;
+    c->px.touch();
     for (uint32_t p = probes; p + 1 > 0 && rc == TW_OK; --p) {  // probes first, the canonical run last
         c->d.tie_mode = p;
         rc = sh_reset(c);
@@ -1182,6 +1283,7 @@ int sh_tie_audit(tw_shard* c, int64_t t_end_us, uint64_t max_events, uint32_t pr
         if (p == 0) break;
     }
     c->d.tie_mode = TW_TIE_FIFO;
+    c->px.touch();  // (the probes ran under other tie modes)
     if (rc != TW_OK) return rc;
     c->tie_flags.assign(c->d.R, 1u);
     for (uint32_t p = 1; p <= probes; ++p)
@@ -1232,6 +1334,7 @@ int sh_set_counter_base(tw_shard* c, uint32_t seq0, uint32_t tid0) {
     if (!c || tid0 == 0) return TW_ERR_INVALID;
     c->seq0 = seq0;
     c->tid0 = tid0;
+    c->px.touch();
     if (c->px.snap.have) {
         HIPCHK(hipSetDevice(c->device));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -1246,6 +1349,7 @@ int sh_set_prefix(tw_shard* c, int on) {
     if (!c) return TW_ERR_INVALID;
     if (!c->loaded) return TW_ERR_STATE;
     c->px.on = on != 0;
+    c->px.touch();
     return TW_OK;
 }
 
@@ -1260,12 +1364,34 @@ int sh_prefix_stats(tw_shard* c, int64_t* t0, uint64_t* events, uint64_t* bytes,
     return TW_OK;
 }
 
+int sh_prefix_clean_stats(tw_shard* c, uint32_t* claimed, uint64_t* rows_skipped, uint64_t* bytes_stored,
+                          uint32_t* verified, uint64_t* audit) {
+    if (!c) return TW_ERR_INVALID;
+    if (!c->loaded) return TW_ERR_STATE;
+    const Prefix::Snap::Clean& cl = c->px.snap.clean;
+    if (claimed) *claimed = c->px.snap.ok ? (uint32_t)cl.slots.size() : 0u;
+    if (rows_skipped) *rows_skipped = c->px.rows_skipped;
+    if (bytes_stored) *bytes_stored = c->px.bytes_stored;
+    if (verified) *verified = c->px.last_verified ? 1u : 0u;
+    if (audit) {
+        unsigned long long n = 0;
+        if (c->px.audited && cl.audit) {
+            HIPCHK(hipSetDevice(c->device));
+            HIPCHK(hipMemcpyAsync(&n, cl.audit, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
+        *audit = n;
+    }
+    return TW_OK;
+}
+
 // The killThread sweep of later tw_run calls (include/timewarp.h tw_set_sweep);
 // on after every tw_load.
 int sh_set_sweep(tw_shard* c, int on) {
     if (!c) return TW_ERR_INVALID;
     if (!c->loaded) return TW_ERR_STATE;
     c->sw.on = on != 0;
+    c->px.touch();
     return TW_OK;
 }
 
@@ -1403,6 +1529,7 @@ int sh_set_stream(tw_shard* c, void* hs) {
     if (!c) return TW_ERR_INVALID;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));  // finish what was queued on the old one
+    c->px.touch();
     c->stream = hs ? (hipStream_t)hs : c->own_stream;
     return TW_OK;
 }
@@ -1870,6 +1997,7 @@ int sh_set_trace(tw_shard* c, uint32_t cap) {
     if (c->lp && !c->lpb) return TW_ERR_INVALID;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
+    c->px.touch();
     if (c->d.trace) {
         HIPCHK(hipFree(c->d.trace));
         c->d.trace = nullptr;

@@ -11,7 +11,10 @@
 //
 //   take    one thread per directory row: replica 0's element -> the snapshot
 //   apply   one workgroup per (row, span of the row): the row's value to the
-//           span's replicas; store-only, 16 B per lane where the row allows
+//           span's replicas; store-only, 16 B per lane where the row allows.
+//           A row the last sweep proved unwritten in every replica since the
+//           apply before is left as it is: its workgroups return
+//   audit   the testing hook's check of those rows (read-only)
 //
 // Every per-replica array is replica-minor, so a row is R contiguous elements.
 // Plain C++ and vector stores only.
@@ -55,7 +58,15 @@ __device__ __forceinline__ uint32_t word_of(uint4 v, uint32_t i) {
 // The value is read once per wave, through the scalar cache (the row is
 // uniform over the workgroup); only rows wider than 16 B (the handler-stack
 // overflow, FXQ > 1) load their quad per lane.
+// quad 1 - 3 of a claimed slot that no replica wrote since the last apply (§3o)
+__device__ __forceinline__ bool row_clean(const PrefixTab& t, uint32_t row) {
+    if (!t.tag) return false;
+    const uint32_t s = t.tag[row];
+    return s != PCL_NO_SLOT && t.cflags[CF_VALID] != 0u && t.dirty[s] == 0;
+}
+
 __global__ void __launch_bounds__(256) tw_prefix_apply(PrefixTab t, uint32_t R) {
+    if (row_clean(t, blockIdx.x)) return;
     const PrefixRow e = t.rows[blockIdx.x];
     const uint32_t es = e.es;
     const uint64_t len = (uint64_t)R * es;
@@ -101,9 +112,37 @@ __global__ void __launch_bounds__(256) tw_prefix_apply(PrefixTab t, uint32_t R) 
     }
 }
 
+// The rows tw_prefix_apply skipped (its own test, on the flags it read), all
+// R elements against the snapshot's quad.  Tagged rows are record quads:
+// 16-byte elements from a 16-byte-aligned address.
+__global__ void __launch_bounds__(256) tw_prefix_audit(PrefixTab t, uint32_t R, unsigned long long* count) {
+    if (!row_clean(t, blockIdx.x)) return;
+    const PrefixRow e = t.rows[blockIdx.x];
+    const uint4 v = *(const uint4*)(t.snap + e.off);
+    const uint4 GAS* dst = (const uint4 GAS*)(uintptr_t)e.dst;
+    const uint64_t i0 = (uint64_t)blockIdx.y * (TW_PREFIX_SPAN / 16u);
+    const uint64_t i1 = i0 + TW_PREFIX_SPAN / 16u < R ? i0 + TW_PREFIX_SPAN / 16u : R;
+    uint32_t bad = 0;
+    for (uint64_t i = i0 + threadIdx.x; i < i1; i += 256u) {
+        const uint4 x = dst[i];
+        bad += (x.x != v.x || x.y != v.y || x.z != v.z || x.w != v.w) ? 1u : 0u;
+    }
+    for (int m = 32; m >= 1; m >>= 1) bad += __shfl_xor(bad, m, 64);
+    if ((threadIdx.x & 63u) == 0 && bad)
+        __hip_atomic_fetch_add(gp(count), (unsigned long long)bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+static_assert(PCL_FL_SHIFT == FL_SHIFT && PCL_EXC_SHIFT == EXC_SHIFT && PCL_F_MAIN == F_MAIN,
+              "prefix_clean.hpp reads the record header of tw_dev.hpp");
+
 }  // namespace
 
 namespace tw {
+
+CleanLayout clean_layout(const Dev& d) {
+    return CleanLayout{(uint64_t)(uintptr_t)d.slots, (uint64_t)(uintptr_t)d.runs, d.R, d.RQ, d.S, d.Cr, d.N, d.n_insns,
+                       (uint32_t)TW_RUNS};
+}
 
 bool prefix_directory(const Dev& d, const uint64_t* sc, uint32_t near_cap, std::vector<PrefixRow>& rows, size_t& bytes) {
     rows.clear();
@@ -164,6 +203,13 @@ hipError_t prefix_apply(const PrefixTab& t, uint32_t R, uint32_t max_es, hipStre
     // rows x spans: the whole chip stores at once (C3: ~70k rows of 256 KB - 1 MB)
     const uint64_t spans = ((uint64_t)R * max_es + TW_PREFIX_SPAN - 1) / TW_PREFIX_SPAN;
     hipLaunchKernelGGL(tw_prefix_apply, dim3(t.n_rows, (uint32_t)(spans ? spans : 1)), dim3(256), 0, st, t, R);
+    return hipGetLastError();
+}
+
+hipError_t prefix_audit(const PrefixTab& t, uint32_t R, uint32_t max_es, unsigned long long* count, hipStream_t st) {
+    if (t.n_rows == 0 || R == 0 || !t.tag) return hipSuccess;
+    const uint64_t spans = ((uint64_t)R * max_es + TW_PREFIX_SPAN - 1) / TW_PREFIX_SPAN;
+    hipLaunchKernelGGL(tw_prefix_audit, dim3(t.n_rows, (uint32_t)(spans ? spans : 1)), dim3(256), 0, st, t, R, count);
     return hipGetLastError();
 }
 

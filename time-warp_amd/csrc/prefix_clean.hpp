@@ -1,0 +1,184 @@
+// prefix_clean.hpp — which rows of the send-free prefix's snapshot an apply
+// may leave unstored, and the table the killThread sweep proves it with
+// (prefix.hip, sweep.hip).  Kept free of HIP so it compiles into a
+// plain host program (tests/prefix_clean_main.cpp, run under ASan / UBSan).
+//
+// Between the snapshot and the image's last sweep time T most threads stay
+// parked: the kill wakes at T and the victims their registers name.  Neither
+// the sweep nor anything else stores quads 1 - 3 of such a record (frames and
+// pending exception value; r0 - r3) unless the header's (w2, w3) -- tid and
+// queued seq -- changes with it (§3o: the writer audit).  The KILL TABLE holds,
+// for every run position whose snapshot entry is at T, what tw_sweep_validate
+// loads there anyway: the run entry, the killer's (w2, w3), its refs and each
+// victim's (w2, w3).  A position is CLAIMABLE if it passes the static side of
+// validate's checks; the slots claimable positions name -- killer and victims
+// -- are the CLAIMED SLOTS, and a replica whose words at a position differ
+// from the table's marks that position's slots dirty.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <unordered_map>
+#include <vector>
+
+#include "sweep_classify.hpp"
+
+namespace tw {
+
+// One row of a replica-minor array: R elements of `es` bytes from device
+// address `dst` (replica 0's element), whose snapshot value lies `off` bytes
+// into the snapshot buffer.  es is 1, 4, 8 or a multiple of 16; off is a
+// multiple of es (of 16 for the wider rows).
+struct PrefixRow {
+    uint64_t dst;
+    uint32_t off;
+    uint32_t es;
+};
+
+// the header fields read here (tw_dev.hpp's FL_SHIFT, EXC_SHIFT, F_MAIN:
+// prefix.hip asserts that they agree)
+constexpr uint32_t PCL_FL_SHIFT = 20u, PCL_EXC_SHIFT = 26u, PCL_F_MAIN = 2u;
+constexpr uint32_t PCL_NO_SLOT = 0xFFFFFFFFu;  // a row's tag: not a claimed slot's quad 1 - 3
+
+// The words of the clean flags, device memory.  CF_ALL_DIRTY: some replica was
+// not checked against the whole table (not attempted, refused, a window the
+// table's does not fit).  CF_VALID: published by the sweep's last kernel --
+// every replica checked, none with work left; consumed by the next apply.
+enum { CF_ALL_DIRTY, CF_VALID, CF_COUNT };
+
+// One run position of the table: four quads, read by the sweep as such.
+struct KillEnt {
+    uint32_t e[4];    // the run entry: time lo, hi, slot, seq
+    uint32_t kw2, kw3, nref, pad;  // the killer's tid and seq; refs (0: the position is not claimable)
+    uint32_t ref[4];  // ref0 slot, tid; ref1 slot, tid
+    uint32_t vw[4];   // victim 0's w2, w3; victim 1's
+};
+static_assert(sizeof(KillEnt) == 64, "KillEnt is four quads");
+
+// A run's table window: ring positions [pos0, pos0 + n) (it may wrap), whose
+// entries are `base`, `base + 1`, .. of the table.
+struct KillWin {
+    uint32_t pos0, n, base, pad;
+};
+
+// the parked layout of sweep_dev.hpp's rec_row and run_row, as numbers
+struct CleanLayout {
+    uint64_t slots, runs;  // device address of replica 0's first record quad / run entry
+    uint64_t R, RQ;        // elements per row; elements between a record's quads
+    uint32_t S, Cr, N, n_insns, n_runs;
+};
+
+struct CleanPlan {
+    std::vector<KillEnt> ents;
+    std::vector<KillWin> win;     // [n_runs]
+    std::vector<uint32_t> slots;  // the claimed slots, ascending
+    uint32_t claimable = 0;       // positions
+};
+
+// The kill table of sweep time T from a snapshot: its bytes, its row
+// directory, replica 0's run heads and counts (rh, rn: n_runs words each) and
+// the image's stub words (n_insns + 1).  Whatever does not resolve -- a row the
+// directory lacks, an operand out of range -- leaves its position unclaimed.
+inline CleanPlan clean_build(const CleanLayout& L, const PrefixRow* rows, size_t n_rows, const uint8_t* snap,
+                             size_t snap_bytes, const uint64_t* rh, const uint64_t* rn, const uint32_t* stub, int64_t T) {
+    CleanPlan p;
+    p.win.assign(L.n_runs, KillWin{0u, 0u, 0u, 0u});
+    if (!rows || !snap || !rh || !rn || !stub || L.R == 0) return p;
+    std::unordered_map<uint64_t, uint32_t> at;  // a 16-byte row's address -> its snapshot offset
+    for (size_t i = 0; i < n_rows; ++i)
+        if (rows[i].es == 16 && (uint64_t)rows[i].off + 16 <= snap_bytes) at.emplace(rows[i].dst, rows[i].off);
+    struct Quad { uint32_t x, y, z, w; };
+    auto quad = [&](uint64_t addr, Quad& q) {
+        auto it = at.find(addr);
+        if (it == at.end()) return false;
+        std::memcpy(&q, snap + it->second, 16);
+        return true;
+    };
+    auto rec = [&](uint32_t slot, uint32_t qd, Quad& q) {
+        return slot < L.S && quad(L.slots + ((uint64_t)qd * L.RQ + (uint64_t)slot * L.R) * 16u, q);
+    };
+    auto reg_of = [](const Quad& q2, const Quad& q3, uint32_t i) {
+        const uint32_t lo = i == 0 ? q2.x : i == 1 ? q2.z : i == 2 ? q3.x : q3.z;
+        const uint32_t hi = i == 0 ? q2.y : i == 1 ? q2.w : i == 2 ? q3.y : q3.w;
+        return ((uint64_t)hi << 32) | lo;
+    };
+    std::vector<uint8_t> claimed(L.S, 0);
+    for (uint32_t j = 0; j < L.n_runs; ++j) {
+        if (rn[j] == 0 || rn[j] > L.Cr || rh[j] >= L.Cr) continue;
+        KillWin w{0u, 0u, (uint32_t)p.ents.size(), 0u};
+        for (uint32_t k = 0; k < (uint32_t)rn[j]; ++k) {
+            uint32_t pos = (uint32_t)rh[j] + k;
+            pos = pos >= L.Cr ? pos - L.Cr : pos;
+            Quad e;
+            const bool have = quad(L.runs + (((uint64_t)j * L.Cr + pos) * L.R) * 16u, e);
+            const bool at_T = have && (int64_t)(((uint64_t)e.y << 32) | e.x) == T;
+            if (!at_T) {
+                if (w.n) break;  // (a run is monotone: the entries at T are one stretch)
+                continue;
+            }
+            if (w.n == 0) w.pos0 = pos;
+            ++w.n;
+            KillEnt ke;
+            std::memset(&ke, 0, sizeof(ke));
+            ke.e[0] = e.x; ke.e[1] = e.y; ke.e[2] = e.z; ke.e[3] = e.w;
+            p.ents.push_back(ke);
+            KillEnt& o = p.ents.back();
+            // the static side of tw_sweep_validate: a live kill-stub wake, no
+            // exception pending, no frames, not main (nor slot 0, which tw_reset writes)
+            Quad h, q2, q3;
+            if (e.z == 0 || !rec(e.z, 0, h) || !rec(e.z, 2, q2) || !rec(e.z, 3, q3)) continue;
+            const uint32_t pc = h.x & 0xFFFFu, sw = stub[pc < L.n_insns ? pc : L.n_insns];
+            if (h.w != e.w || h.w == 0 || (h.x >> PCL_EXC_SHIFT) != 0 || !(sw & SWB_VALID) ||
+                (((h.x >> PCL_FL_SHIFT) & 0x3Fu) & PCL_F_MAIN) || ((h.x >> 16) & 15u) != 0 || h.y >= L.N)
+                continue;
+            const uint32_t nref = (sw & SWB_TWO) ? 2u : 1u;
+            const uint64_t ref[2] = {reg_of(q2, q3, SWB_RA0(sw)), nref > 1 ? reg_of(q2, q3, SWB_RA1(sw)) : 0ull};
+            bool ok = true;
+            for (uint32_t v = 0; v < nref && ok; ++v) {
+                // a snapshot thread with that tid, queued, not main, not slot 0, not the killer
+                const uint32_t ts = (uint32_t)ref[v], tid = (uint32_t)(ref[v] >> 32);
+                Quad vh;
+                ok = ts != 0 && ts != e.z && rec(ts, 0, vh) && vh.z == tid && vh.w != 0 &&
+                     !(((vh.x >> PCL_FL_SHIFT) & 0x3Fu) & PCL_F_MAIN);
+                if (ok) {
+                    o.ref[2 * v] = ts; o.ref[2 * v + 1] = tid;
+                    o.vw[2 * v] = vh.z; o.vw[2 * v + 1] = vh.w;
+                }
+            }
+            if (!ok) {
+                std::memset(o.ref, 0, sizeof(o.ref));
+                std::memset(o.vw, 0, sizeof(o.vw));
+                continue;
+            }
+            o.kw2 = h.z; o.kw3 = h.w; o.nref = nref;
+            ++p.claimable;
+            claimed[e.z] = 1;
+            for (uint32_t v = 0; v < nref; ++v) claimed[o.ref[2 * v]] = 1;
+        }
+        if (w.n) p.win[j] = w;
+    }
+    for (uint32_t s = 0; s < L.S; ++s)
+        if (claimed[s]) p.slots.push_back(s);
+    return p;
+}
+
+// The tag of every directory row: the slot whose quad 1, 2 or 3 it is when that
+// slot is claimed, PCL_NO_SLOT for every other row.
+inline std::vector<uint32_t> clean_tags(const CleanLayout& L, const PrefixRow* rows, size_t n_rows,
+                                        const std::vector<uint32_t>& slots) {
+    std::vector<uint32_t> tag(n_rows, PCL_NO_SLOT);
+    std::vector<uint8_t> claimed(L.S, 0);
+    for (uint32_t s : slots)
+        if (s < L.S) claimed[s] = 1;
+    const uint64_t span = L.RQ * 16u;  // bytes between a record's quads
+    for (size_t i = 0; i < n_rows && L.R && span; ++i) {
+        if (rows[i].es != 16 || rows[i].dst < L.slots) continue;
+        const uint64_t b = rows[i].dst - L.slots, q = b / span, in = b % span;
+        if (q < 1 || q > 3 || in % (L.R * 16u) != 0) continue;
+        const uint64_t s = in / (L.R * 16u);
+        if (s < L.S && claimed[s]) tag[i] = (uint32_t)s;
+    }
+    return tag;
+}
+
+}  // namespace tw

@@ -78,6 +78,7 @@ struct Sweep {
     bool on = true;                     // tw_set_sweep; on after every load
     tw::SweepTab tab{};
     std::vector<int64_t> times;
+    std::vector<uint32_t> stub_h;       // host copy of tab.stub (the kill table's builder reads it)
     uint32_t done = 0;
     unsigned long long* h = nullptr;    // pinned; outlives loads
     uint64_t last[3] = {0, 0, 0};
@@ -106,21 +107,55 @@ struct Prefix {
         tw::PrefixTab tab{};
         uint32_t max_es = 0;
         uint64_t events = 0;            // events of a replica at the snapshot
-        size_t bytes = 0;               // bytes the apply writes per replica
+        size_t bytes = 0;               // the snapshot's bytes per replica
+        // Rows the apply may leave unstored (prefix_clean.hpp): the
+        // kill table of sweep time T = Sweep::times[stop], built from this
+        // snapshot; `dev` null: none.  One device block (table, windows, row
+        // tags, dirty bytes, flag words, the audit's count) and the pinned
+        // copy of the dirty bytes and flag words a verifying run leaves.
+        struct Clean {
+            void* dev = nullptr;
+            const tw::KillEnt* kill = nullptr;
+            const tw::KillWin* kwin = nullptr;
+            const uint32_t* tag = nullptr;
+            uint8_t* dirty = nullptr;           // [S], then the CF_COUNT flag words
+            uint32_t* cflags = nullptr;
+            unsigned long long* audit = nullptr;
+            uint8_t* h = nullptr;               // pinned: [S] dirty bytes + flag words
+            uint32_t S = 0, stop = 0;
+            std::vector<uint32_t> slots;        // the claimed slots
+        } clean;
     } snap;
     uint32_t last = TW_PREFIX_NOT_ELIGIBLE;  // what the last tw_run did
     double ms = 0.0;                    // device time of the last tw_run's apply
+    // §3o's validity rule.  chain: every replica's state derives from an apply
+    // of this snapshot since the last tw_reset and only tw_run has written it
+    // since; such a run's sweep at the table's time checks the replicas.
+    // verified: the last tw_run's sweep published CF_VALID and nothing but
+    // tw_reset and read-only calls came since: the next apply may skip rows.
+    bool chain = false, verified = false;
+    bool audit = false;                 // the testing hook TW_TEST_PREFIX_AUDIT (read when the context is made)
+    // of the last apply: rows left unstored, bytes stored per replica; whether the last tw_run verified
+    uint64_t rows_skipped = 0, bytes_stored = 0;
+    bool last_verified = false;
+    bool audited = false;               // the last apply ran the hook's audit (its count: Clean::audit)
 
+    // anything but tw_reset, tw_run and a read-only call: the flags no longer
+    // describe the replicas
+    void touch() { chain = verified = false; }
     // forget the cached snapshot (tw_load, tw_set_tie_mode, tw_set_counter_base)
     void drop() {
         if (snap.tab.rows) (void)hipFree((void*)snap.tab.rows);
         if (snap.tab.snap) (void)hipFree(snap.tab.snap);
+        if (snap.clean.dev) (void)hipFree(snap.clean.dev);
+        if (snap.clean.h) (void)hipHostFree(snap.clean.h);
         snap = Snap{};
+        touch();
     }
     void unload() {
         drop();
         Prefix z;
-        z.last = last; z.ms = ms;
+        z.last = last; z.ms = ms; z.audit = audit;
         *this = z;
     }
 };

@@ -41,6 +41,11 @@ TW_HIDDEN int sh_sweep_stats(tw_shard* c, uint64_t* killers, uint64_t* victims, 
 // (TW_PREFIX_*) and its apply's device time
 TW_HIDDEN int sh_set_prefix(tw_shard* c, int on);
 TW_HIDDEN int sh_prefix_stats(tw_shard* c, int64_t* t0, uint64_t* events, uint64_t* bytes, uint32_t* last, double* ms);
+// rows the apply leaves unstored (prefix_clean.hpp): the snapshot's claimed
+// slots, the last sh_run's apply (rows skipped, bytes stored per replica),
+// whether that run verified, the testing hook's mismatch count
+TW_HIDDEN int sh_prefix_clean_stats(tw_shard* c, uint32_t* claimed, uint64_t* rows_skipped, uint64_t* bytes_stored,
+                                    uint32_t* verified, uint64_t* audit);
 TW_HIDDEN int sh_set_trace(tw_shard* c, uint32_t cap);
 TW_HIDDEN int sh_read_trace(tw_shard* c, uint32_t replica, tw_trace_rec* out, size_t cap, uint64_t* n_emitted);
 // tw_measure on one shard: sh_measure_state is its state check alone

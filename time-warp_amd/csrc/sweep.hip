@@ -117,13 +117,54 @@ struct Killer {
     uint32_t sw;   // stub word of its resume pc
     uint64_t ref0, ref1;  // its victims' refs (ref1: of a stub with two throwTos)
     uint32_t nref;
+    // the kill table's claimable position here (§3o; tab false: none): whether
+    // the replica's killer (w2, w3) and run entry are the table's, its second
+    // and third quad and its killer's slot (the last four: validate's)
+    bool tab, hit, ent;
+    uint4 ka, kr;
+    uint32_t kslot;
 };
 
-__device__ __forceinline__ bool load_killer(const Dev& c, const SweepTab& t, uint32_t r, uint4 e, int64_t T, Killer& k) {
+// run j's window of the kill table (n == 0: no table)
+__device__ __forceinline__ KillWin kill_win(const SweepTab& t, uint32_t j) {
+    return t.kill ? t.kwin[j] : KillWin{0u, 0u, 0u, 0u};
+}
+
+// `pos`: the entry's ring position, `kw`: its run's table window.  Where the
+// killer's (w2, w3) are the table's, its register quads are the snapshot's
+// (§3o) and the refs come from the table: quads 2 and 3 are not loaded.
+// (KEEP: validate goes on comparing with the table's quads; apply only takes the refs)
+template <bool KEEP>
+__device__ __forceinline__ bool load_killer(const Dev& c, const SweepTab& t, uint32_t r, uint4 e, int64_t T, Killer& k,
+                                            uint32_t pos, const KillWin& kw) {
     k.nref = 0;
     k.sw = 0;
+    k.tab = k.hit = k.ent = false;
+    k.ka = k.kr = make_uint4(0u, 0u, 0u, 0u);
+    k.kslot = 0;
     if (ent_t(e) != T || e.z >= c.S) return false;
     k.h = *rec_q(c, e.z, r, 0);
+    uint64_t tr0 = 0, tr1 = 0;  // the table's refs
+    const uint32_t tk = pos >= kw.pos0 ? pos - kw.pos0 : pos + c.Cr - kw.pos0;
+    if (tk < kw.n) {
+        const uint4 GAS* kp = (const uint4 GAS*)gp(t.kill) + (size_t)(kw.base + tk) * 4u;
+        const uint4 ka = kp[1];
+        k.tab = ka.z != 0u;
+        if (k.tab) {
+            // (a tid names one thread and a thread keeps its slot: the killer's
+            // (w2, w3) alone say that its registers are the snapshot's; validate
+            // compares the entry too, for the position's dirty marks)
+            const uint4 kr = kp[2];
+            k.hit = ka.x == k.h.z && ka.y == k.h.w;
+            tr0 = ((uint64_t)kr.y << 32) | kr.x;
+            tr1 = ((uint64_t)kr.w << 32) | kr.z;
+            if (KEEP) {
+                const uint4 te = kp[0];
+                k.ent = te.x == e.x && te.y == e.y && te.z == e.z && te.w == e.w;
+                k.ka = ka; k.kr = kr; k.kslot = te.z;
+            }
+        }
+    }
     const uint32_t pc = k.h.x & 0xFFFFu;
     k.sw = gp(t.stub)[pc < c.n_insns ? pc : c.n_insns];
     const uint32_t fl = (k.h.x >> FL_SHIFT) & 0x3Fu;
@@ -138,10 +179,10 @@ __device__ __forceinline__ bool load_killer(const Dev& c, const SweepTab& t, uin
     // (not `n2 ? *rec_q(..) : z`: the conditional's uint4 temporary stays in
     // memory, a scratch frame and a 16-byte scratch store per entry in both kernels)
     uint4 q2 = z, q3 = z;
-    if (n2) q2 = *rec_q(c, e.z, r, 2);
-    if (n3) q3 = *rec_q(c, e.z, r, 3);
-    k.ref0 = reg_of(q2, q3, a0);
-    k.ref1 = two ? reg_of(q2, q3, a1) : 0ull;
+    if (n2 && !k.hit) q2 = *rec_q(c, e.z, r, 2);
+    if (n3 && !k.hit) q3 = *rec_q(c, e.z, r, 3);
+    k.ref0 = k.hit ? tr0 : reg_of(q2, q3, a0);
+    k.ref1 = !two ? 0ull : k.hit ? tr1 : reg_of(q2, q3, a1);
     k.nref = two ? 2u : 1u;
     return true;
 }
@@ -165,19 +206,43 @@ __global__ void __launch_bounds__(64) tw_sweep_validate(Dev c, SweepTab t, int64
     bool bad = false;
     for (uint32_t j = 0; j < TW_RUNS && !bad; ++j) {
         const uint32_t pl = *acc_at(t, c, SW_PL0 + j, r), rh = (uint32_t)sc[(SC_RH0 + j) * R];
+        // the kill table's window of this run (§3o): the replica's prefix must
+        // hold all of it, or some position goes unchecked
+        const KillWin kw = kill_win(t, j);
+        if (kw.n) {
+            const uint32_t off = kw.pos0 >= rh ? kw.pos0 - rh : kw.pos0 + c.Cr - rh;
+            if ((uint64_t)off + kw.n > pl) gp(t.cflags)[CF_ALL_DIRTY] = 1u;
+        }
         for (uint32_t i = blockIdx.y; i < pl && !bad; i += gridDim.y) {
             uint32_t pos = rh + i;
             pos = pos >= c.Cr ? pos - c.Cr : pos;
+            const uint4 e = *run_ent(c, j, pos, r);
             Killer k;
-            if (!load_killer(c, t, r, *run_ent(c, j, pos, r), T, k) || !owner_ok(c, r, k.h)) { bad = true; break; }
+            if (!load_killer<true>(c, t, r, e, T, k, pos, kw) || !owner_ok(c, r, k.h)) { bad = true; break; }
             ++nk;
+            // A claimable table position: the entry, the killer's (w2, w3), the
+            // refs and each victim's (w2, w3) as the snapshot had them, or the
+            // position's slots are dirty.  (A replica that turns bad is refused:
+            // finalize sets CF_ALL_DIRTY for it.)
+            const bool tab = k.tab;
+            bool mis = tab && (!k.hit || !k.ent || k.ka.z != k.nref);
+            const uint4 ka = k.ka, kr = k.kr;
+            uint4 kv = make_uint4(0u, 0u, 0u, 0u);
+            if (tab) {
+                const uint32_t tk = pos >= kw.pos0 ? pos - kw.pos0 : pos + c.Cr - kw.pos0;
+                kv = ((const uint4 GAS*)gp(t.kill) + (size_t)(kw.base + tk) * 4u)[3];
+            }
+            const uint32_t kslot = k.kslot;
 #pragma unroll
             for (uint32_t v = 0; v < 2; ++v) {
                 if (v >= k.nref) break;
                 const uint64_t ref = v ? k.ref1 : k.ref0;
                 const uint32_t ts = (uint32_t)ref, tid = (uint32_t)(ref >> 32);
+                // (the table's refs are below S: a ref at or above it is a mismatch here)
+                mis = mis || (tab && (ts != (v ? kr.z : kr.x) || tid != (v ? kr.w : kr.y)));
                 if (ts >= c.S) continue;                      // a stale ref: no-op (Lane::throw_to)
                 const uint4 h = *rec_q(c, ts, r, 0);
+                mis = mis || (tab && (h.z != (v ? kv.z : kv.x) || h.w != (v ? kv.w : kv.y)));
                 if (h.z != tid) continue;                     // dead: slot free or reused
                 const uint32_t fl = (h.x >> FL_SHIFT) & 0x3Fu, nfr = (h.x >> 16) & 15u, pc = h.x & 0xFFFFu;
                 bool ok = (fl & F_STARTED) && !(fl & F_MAIN) && (h.x >> EXC_SHIFT) == 0 && nfr <= 2 && h.w != 0 &&
@@ -190,6 +255,11 @@ __global__ void __launch_bounds__(64) tw_sweep_validate(Dev c, SweepTab t, int64
                 }
                 if (!ok) { bad = true; break; }
                 ++nh;
+            }
+            if (mis) {  // (the table's slots, all below S: plain byte stores, rare)
+                gp(t.dirty)[kslot] = 1;
+                gp(t.dirty)[kr.x] = 1;
+                if (ka.z > 1u) gp(t.dirty)[kr.z] = 1;
             }
         }
     }
@@ -226,12 +296,13 @@ __global__ void __launch_bounds__(64) tw_sweep_apply(Dev c, SweepTab t, int64_t 
     uint32_t nv = 0;
     for (uint32_t j = 0; j < TW_RUNS; ++j) {
         const uint32_t pl = *acc_at(t, c, SW_PL0 + j, r), rh = (uint32_t)sc[(SC_RH0 + j) * R];
+        const KillWin kw = kill_win(t, j);
         for (uint32_t i = blockIdx.y; i < pl; i += gridDim.y) {
             uint32_t pos = rh + i;
             pos = pos >= c.Cr ? pos - c.Cr : pos;
             const uint4 e = *run_ent(c, j, pos, r);
             Killer k;
-            if (!load_killer(c, t, r, e, T, k)) continue;  // (validated: cannot happen)
+            if (!load_killer<false>(c, t, r, e, T, k, pos, kw)) continue;  // (validated: cannot happen)
             // the kill wake's pop: END (Lane::die_prep); its resume term goes out below
             if (((k.h.x >> FL_SHIFT) & 0x3Fu) & F_OWNS) gp(c.bind_rel)[(size_t)k.h.y * R + r] = k.h.z;
             *rec_q(c, e.z, r, 0) = make_uint4(k.h.x | (F_STARTED << FL_SHIFT), k.h.y, 0xFFFFFFFFu, 0u);
@@ -321,9 +392,14 @@ __global__ void __launch_bounds__(256) tw_sweep_finalize(Dev c, SweepTab t, int6
                 }
             }
             if (live == 0) sc[SC_STATUS * R] = TW_REP_DONE;  // whileM_ notDone (TimedT.hs:239)
-        } else if (bad != 2u) {
-            ref = 1;
-            next = T;
+        } else {
+            // not attempted, refused or over a cap: it was not checked against the
+            // whole kill table, and may pop its events one by one later (§3o)
+            if (t.kill) gp(t.cflags)[CF_ALL_DIRTY] = 1u;
+            if (bad != 2u) {
+                ref = 1;
+                next = T;
+            }
         }
         // (the event kernel's own rule for a lane it counts in n_active)
         if (sc[SC_STATUS * R] == TW_REP_RUNNING &&
@@ -345,8 +421,12 @@ __global__ void __launch_bounds__(256) tw_sweep_finalize(Dev c, SweepTab t, int6
 }
 
 // the stop is done (a kernel of its own: every block of finalize reads the gate)
+// ... and, with a kill table: every replica was checked against all of it and
+// none has work left that could write a record after the check (§3o)
 __global__ void tw_sweep_mark(Dev c, SweepTab t, uint32_t expect) {
-    if (sweep_gate(c, t, expect)) gp(t.stats)[SWS_FIRED] = (unsigned long long)expect + 1ull;
+    if (!sweep_gate(c, t, expect)) return;
+    if (t.kill) gp(t.cflags)[CF_VALID] = (gp(t.cflags)[CF_ALL_DIRTY] == 0u && gp(t.stats)[SWS_LEFT] == 0ull) ? 1u : 0u;
+    gp(t.stats)[SWS_FIRED] = (unsigned long long)expect + 1ull;
 }
 
 }  // namespace

@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "tw_dev.hpp"
+#include "prefix_clean.hpp"
 
 namespace tw {
 
@@ -26,6 +27,12 @@ struct SweepTab {
     uint32_t* acc;              // [SW_COUNT][R]
     unsigned long long* stats;  // [SWS_COUNT]
     uint32_t near_cap;          // entries of the near spill per replica
+    // The kill table of this sweep's time and the flags it proves clean rows
+    // with (prefix_clean.hpp); kill null: none, the sweep as ever.
+    const KillEnt* kill;        // the table's positions
+    const KillWin* kwin;        // [TW_RUNS] each run's window of them
+    uint8_t* dirty;             // [S] a claimed slot some replica's words did not match
+    uint32_t* cflags;           // [CF_COUNT] (prefix_dev.hpp)
 };
 
 // The parked layout the event kernel's epilogue leaves (shared with prefix.hip):

@@ -32,7 +32,8 @@ EXPORTS = ["tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_ru
            "tw_set_stream", "tw_lp_exchange_setup", "tw_lp_loop_begin", "tw_lp_tick", "tw_lp_tick_import",
            "tw_lp_tick_end", "tw_lp_progress", "tw_lp_run_windows", "tw_lpb_load", "tw_lpb_windows",
            "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms", "tw_set_sweep", "tw_sweep_stats",
-           "tw_set_prefix", "tw_prefix_stats", "tw_set_measure_keys", "tw_measure_phases_ms"]
+           "tw_set_prefix", "tw_prefix_stats", "tw_set_measure_keys", "tw_measure_phases_ms",
+           "tw_prefix_clean_stats"]
 GEOMETRIES = ("dense", "sparse", "half", "wave", "lp", "narrow", "lpb", "compact")  # TW_GEO_* order
 
 # tw_trace_rec (include/timewarp.h)
@@ -118,6 +119,10 @@ def load_library(path: Optional[str] = None):
     lib.tw_set_prefix.argtypes = [C.c_void_p, C.c_int]
     lib.tw_prefix_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+    if hasattr(lib, "tw_prefix_clean_stats"):  # (an older in-tree build under TW_LIB lacks it)
+        lib.tw_prefix_clean_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        lib.tw_prefix_clean_stats.restype = C.c_int
     for name in ("tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_run", "tw_set_tie_mode", "tw_load", "tw_reset", "tw_run", "tw_read_results", "tw_read_hashes", "tw_read_final",
                  "tw_last_launch_ms", "tw_lp_load", "tw_lp_window", "tw_lp_take_outbox", "tw_lp_inject",
                  "tw_lp_results", "tw_set_trace", "tw_read_trace", "tw_tie_audit", "tw_set_counter_base",
@@ -377,6 +382,17 @@ class Engine:
                "tw_prefix_stats")
         return {"t0": int(t0.value), "events": int(ev.value), "bytes": int(by.value),
                 "last": self.PREFIX_USE[use.value], "apply_ms": float(ms.value)}
+
+    def prefix_clean_stats(self) -> dict:
+        """Rows the apply leaves unstored (tw_prefix_clean_stats): the cached
+        snapshot's claimed slots, the rows the last run's apply skipped and the
+        bytes it stored per replica, whether the last run verified, and the
+        testing hook's count of skipped elements that differed (0)."""
+        cl, rows, by, ver, bad = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        _check(self.lib.tw_prefix_clean_stats(self.ctx, C.byref(cl), C.byref(rows), C.byref(by), C.byref(ver),
+                                              C.byref(bad)), "tw_prefix_clean_stats")
+        return {"claimed_slots": int(cl.value), "rows_skipped": int(rows.value), "bytes_stored": int(by.value),
+                "verified": bool(ver.value), "audit_mismatches": int(bad.value)}
 
     def set_counter_base(self, seq0: int, tid0: int = 1) -> "Engine":
         """Testing hook: start the 32-bit insertion / thread counters at these

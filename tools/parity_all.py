@@ -12,7 +12,10 @@ the oracle's canonical (t, seq) run (oracle/timedt_oracle.cpp, TimedT.hs:
   C5  hotspot 256 senders -> 1 x 4,096 replicas, 1,000 messages (lpb, with
       the data-parallel due-run batch tw_lp_batch on)
 
-usage: python tools/parity_all.py [c3|c2|c5 ...] [--threads N] [--chunk N]
+usage: python tools/parity_all.py [c3|c2|c5 ...] [--threads N] [--chunk N] [--resets K]
+--resets K runs K further reset / run pairs before the results are read, so
+that what is compared is a step that applied the cached send-free prefix
+(K >= 2: an apply that skips the rows the step before it verified).
 Writes one JSON line per config (and progress lines to stderr every chunk, so
 a long oracle run is never silent); exit 1 on any mismatch.
 """
@@ -42,7 +45,7 @@ def build(cfg, drawer):
     raise SystemExit(f"unknown config {cfg}")
 
 
-def check(cfg, threads, chunk):
+def check(cfg, threads, chunk, resets=0):
     import functools
 
     import oracle  # the parity checker
@@ -57,6 +60,10 @@ def check(cfg, threads, chunk):
             e.set_tie_mode(tie)
         e.reset()
         st = e.run()
+        for _ in range(resets):
+            e.reset()
+            st = e.run()
+        prefix = dict(e.prefix_stats(), **e.prefix_clean_stats()) if geo is None else None
         res, hashes = e.results(), e.hashes()
         geometry = e.geometry()
         bat = e.lpb_batch() if geometry == "lpb" else None
@@ -94,6 +101,10 @@ def check(cfg, threads, chunk):
            "mismatching_replicas_by_field": bad_fields, "mismatching_hash_rows": bad_hash_reps,
            "first_mismatch": first_bad, "bit_exact": bool(ok), "oracle_threads": threads,
            "oracle_s": round(time.perf_counter() - t1, 1), "gpu_s": round(gpu_s, 1)}
+    if resets:
+        out["further_reset_run_pairs"] = resets
+    if prefix is not None:
+        out["prefix"] = prefix
     if bat is not None:
         out["lp_batch"] = {"batched_due_records": int(bat[0]), "due_records": int(bat[1])}
     print(json.dumps(out), flush=True)
@@ -105,6 +116,7 @@ def main():
     ap.add_argument("configs", nargs="*", default=["c3", "c2", "c5"])
     ap.add_argument("--threads", type=int, default=0, help="oracle threads (default: nproc)")
     ap.add_argument("--chunk", type=int, default=8192, help="replicas per oracle call (one progress line each)")
+    ap.add_argument("--resets", type=int, default=0, help="further reset / run pairs before the results are read")
     a = ap.parse_args()
     threads = a.threads
     if threads <= 0:
@@ -114,7 +126,7 @@ def main():
         threads = host_cpu()[0]
     ok = True
     for cfg in a.configs:
-        ok = check(cfg, threads, a.chunk if cfg != "c2" else max(a.chunk, 65536)) and ok
+        ok = check(cfg, threads, a.chunk if cfg != "c2" else max(a.chunk, 65536), a.resets) and ok
     sys.exit(0 if ok else 1)
 
 

@@ -3,12 +3,16 @@
 
     python tools/prefix_probe.py off   [bench.py arguments]
     python tools/prefix_probe.py stats [bench.py arguments]
+    python tools/prefix_probe.py noskip [bench.py arguments]
 
 `off` calls tw_set_prefix(0) behind every load, so the result line is the A/B
 arm "this library without the prefix" measured by bench.py's own loop.  `stats`
 leaves the prefix on and prints tw_prefix_stats after the last step to stderr
 (T0, the snapshot's events and bytes per replica, the apply's device time and
-its store rate over the batch).  The result line is bench.py's in both cases.
+its store rate over the batch; tw_prefix_clean_stats: the claimed slots, the
+rows the last apply skipped and the bytes it stored).  `noskip` leaves the
+prefix on but makes every apply store every row (a tw_set_prefix(1) before
+each run: any setter ends the last run's verification).  The result line is bench.py's in both cases.
 """
 import os
 import sys
@@ -18,7 +22,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "time-warp_amd")]
 
 
 def main():
-    if len(sys.argv) < 2 or sys.argv[1] not in ("off", "stats"):
+    if len(sys.argv) < 2 or sys.argv[1] not in ("off", "stats", "noskip"):
         raise SystemExit(__doc__)
     mode = sys.argv.pop(1)
     import bench
@@ -37,11 +41,23 @@ def main():
             st = self.prefix_stats()
             if st["apply_ms"] > 0:
                 st["apply_TBps"] = st["bytes"] * self.scn.n_replicas / (st["apply_ms"] * 1e-3) / 1e12
+                # (what the apply stored: tw_prefix_clean_stats' bytes, not the snapshot's)
+                cs = self.prefix_clean_stats()
+                st["stored_TBps"] = cs["bytes_stored"] * self.scn.n_replicas / (st["apply_ms"] * 1e-3) / 1e12
+                st.update(cs)
             print(f"[prefix] {st}", file=sys.stderr, flush=True)
         close(self)
 
+    run = Engine.run
+
+    def run_noskip(self, *a, **k):
+        self.set_prefix(True)
+        return run(self, *a, **k)
+
     if mode == "off":
         Engine.load = load_off
+    elif mode == "noskip":
+        Engine.run = run_noskip
     else:
         Engine.close = close_stats
     bench.main()
