@@ -44,6 +44,7 @@
 #include "tw_dev.hpp"
 #include "shard.hpp"
 #include "run_state.hpp"
+#include "load_plan.hpp"
 #include "sweep_classify.hpp"
 #include "sweep_dev.hpp"
 #include "prefix_classify.hpp"
@@ -53,68 +54,42 @@
 
 // ======================================================================= C ABI
 struct tw_shard {
+    // the context's own: made by sh_create, outlive every load
     int device = 0;
-    hipStream_t stream = nullptr;
-    Dev d{};
+    hipStream_t stream = nullptr;     // where everything runs (tw_set_stream may replace it)
+    hipStream_t own_stream = nullptr; // the context's stream
+    uint32_t* h_active = nullptr;     // pinned
+    uint32_t seq0 = 0, tid0 = 1;      // tw_set_counter_base: the context's, not the load's
+    // pops per lane per tick of the device loop (TW_LP_TICK_BUDGET overrides it,
+    // for tests: a small budget makes windows take several ticks), and the LP
+    // launches' grid limit (above it they walk the list; TW_LP_GRID env): read
+    // at tw_lp_loop_begin, kept since
+    uint32_t lp_budget = 1u << 14;
+    uint32_t lp_grid = TW_LP_GRID;
+    LaunchTimes times;                // of the last tw_run (tw_last_launch_ms, tw_stats.kernel_ms); the event pool
+    // the load: every field below is written by each load_common (describe,
+    // allocate) and means nothing while `loaded` is false
     bool loaded = false;
-    std::vector<void*> allocs;
-    uint32_t* h_active = nullptr;  // pinned
-    // tw_run's statistics reduced on the device (tw_stats_kernel): the events
-    // column at the run's start, the 8 result words, their pinned host copy
-    uint64_t* st_ev0 = nullptr;
-    unsigned long long* st_out = nullptr;
-    unsigned long long* h_st = nullptr;
+    Dev d{};
+    std::vector<void*> allocs;        // the load's device memory (dalloc); freed by free_all
+    Dev* d_dev = nullptr;             // device copy of d (the wave kernel reads it through the scalar cache)
+    size_t lds_bytes = 0;
+    int geo = TW_GEO_DENSE;  // a replica geometry's TW_GEO_* (LP contexts: dense, unused; with_geo)
     uint32_t main_pc = 0, main_node = 0;
     int64_t* main_regs = nullptr;  // device copies for tw_reset
     int64_t* nv_init = nullptr;
     uint32_t* listen_init = nullptr;
-    size_t lds_bytes = 0;
-    int geo = TW_GEO_DENSE;  // a replica geometry's TW_GEO_* (LP contexts: dense, unused; with_geo)
-    // LP mode
-    bool lp = false;
-    bool lpb = false;               // batched LP (tw_lpb_load): R = nodes x replicas
-    uint32_t n_rep = 1;             // replicas batched per node
-    bool heavy_ok = false;          // some node's inbox can exceed TW_LIGHT (tw_lp_due runs)
-    uint64_t lpb_windows = 0, lpb_ticks = 0;  // of the last batched-LP tw_run
-    bool lpb_fresh = false;         // tw_reset since the last batched-LP tw_run: every counter is 0
-    bool has_ph1 = false;           // two-phase windows (Dev::phase)
-    uint4* foreign = nullptr;      // [out_cap][2]
-    uint32_t* n_foreign = nullptr;
-    uint4* staging = nullptr;      // inject staging [out_cap][2]
-    LaunchTimes times;              // of the last tw_run (tw_last_launch_ms, tw_stats.kernel_ms)
     std::vector<uint32_t> tie_flags;  // tw_tie_audit, per replica
-    Dev* d_dev = nullptr;             // device copy of d (the wave kernel reads it through the scalar cache)
-    uint32_t seq0 = 0, tid0 = 1;      // tw_set_counter_base
-    hipStream_t own_stream = nullptr; // the context's stream (tw_set_stream may replace `stream`)
-    // device-driven windows (tw_lp_exchange_setup / sh_lp_exchange_own):
-    // blocks of ex_cap records (the stride) of which the first ex_cap_eff go
-    // over the wire this tick (<= ex_cap; the library loop adapts it)
-    uint32_t ex_world = 1, ex_rank = 0, ex_cap = 0, ex_cap_eff = 0;
-    uint32_t* ex_starts = nullptr;    // device, world + 1
-    uint4* ex_send = nullptr;         // caller's device buffers (or ex_own's)
-    uint4* ex_recv = nullptr;
-    int64_t* ex_red = nullptr;        // caller's (or red_own, or ex_own's)
-    int64_t* red_own = nullptr;
-    void* ex_own = nullptr;           // library-owned send | recv | red (sh_lp_exchange_own)
-    void* ex_carry = nullptr;         // Dev::carry + carry_n
-    int64_t* win_buf = nullptr;       // the device loop's WN_* words
-    int64_t* h_win = nullptr;         // pinned host copy of them + lp_err (tw_lp_progress)
-    bool loop_ready = false;
-    // sh_lp_run_windows: TW_GRAPH_TICKS ticks + the progress copy captured as
-    // one hipGraph (a tick is 4-8 short kernels: launched one by one, the host's
-    // enqueue rate left the device idle between them), re-captured when the
-    // launch arguments it holds change (tick_gkey)
-    hipGraphExec_t tick_graph = nullptr;
-    std::vector<unsigned char> tick_gkey;
-    // pops per lane per tick of the device loop (TW_LP_TICK_BUDGET overrides it,
-    // for tests: a small budget makes windows take several ticks)
-    uint32_t lp_budget = 1u << 14;
-    uint32_t lp_grid = TW_LP_GRID;  // LP launches above this many workgroups walk the list (TW_LP_GRID env)
+    // the features (run_state.hpp): each resets itself at free_all
+    LpMode lpm;
+    StatBuf st;
+    Exchange ex;
+    TickGraph tg;
     Sweep sw;
     Prefix px;
     Dev dwin() const {                // the descriptor the device loop's kernels get
         Dev x = d;
-        x.win = win_buf;
+        x.win = ex.win_buf;
         return x;
     }
 };
@@ -131,37 +106,17 @@ int dalloc(tw_shard* c, T** p, size_t n) {
     return TW_OK;
 }
 
+// unload: the load's device memory, then every feature's own
 void free_all(tw_shard* c) {
     for (void* p : c->allocs) (void)hipFree(p);
     c->allocs.clear();
     c->px.unload();
     c->sw.unload();
-    if (c->d.trace) (void)hipFree(c->d.trace);
-    if (c->d.trace_n) (void)hipFree(c->d.trace_n);
-    c->d.trace = nullptr;
-    c->d.trace_n = nullptr;
-    c->d.trace_cap = 0;
-    if (c->ex_starts) (void)hipFree(c->ex_starts);
-    if (c->ex_own) (void)hipFree(c->ex_own);
-    if (c->ex_carry) (void)hipFree(c->ex_carry);
-    c->ex_starts = nullptr;
-    c->ex_own = c->ex_carry = nullptr;
-    c->d.carry = nullptr;
-    c->d.carry_n = nullptr;
-    c->d.carry_cap = 0;
-    c->ex_send = c->ex_recv = nullptr;
-    c->ex_red = c->red_own = nullptr;
-    c->win_buf = nullptr;
-    c->ex_world = 1;
-    c->ex_rank = c->ex_cap = c->ex_cap_eff = 0;
-    c->loop_ready = false;
-    if (c->st_ev0) (void)hipFree(c->st_ev0);
-    if (c->st_out) (void)hipFree(c->st_out);
-    c->st_ev0 = nullptr;
-    c->st_out = nullptr;
-    if (c->tick_graph) (void)hipGraphExecDestroy(c->tick_graph);
-    c->tick_graph = nullptr;
-    c->tick_gkey.clear();
+    trace_release(c->d);
+    c->ex.unload(c->d);
+    c->st.unload();
+    c->tg.unload();
+    c->lpm.unload();
     c->loaded = false;
 }
 
@@ -195,7 +150,7 @@ using GeoLP = Geo<true, TW_WG_LP, TW_NEAR_LP, 64, true, false, TW_NEAR_LP>;
 // f(description) of the context's geometry (not the wave geometry's)
 template <class F>
 static auto with_geo(const tw_shard* c, F&& f) {
-    if (c->lp) return f(GeoLP{});
+    if (c->lpm.lp) return f(GeoLP{});
     switch (c->geo) {
     case TW_GEO_SPARSE: return f(GeoSparse{});
     case TW_GEO_HALF: return f(GeoHalf{});
@@ -263,7 +218,7 @@ static void launch_run(tw_shard* c, hipStream_t st, int64_t t_end, uint64_t limi
     uint32_t blocks = (grid && !G::LP) ? grid : (uint32_t)((c->d.R + G::WG - 1) / G::WG);
     Variant v{false, false, use_ip<G>(c), false};
     if constexpr (G::LP) {
-        v = Variant{blocks > c->lp_grid, c->d.rw && c->d.win, false, c->lpb && c->d.trace_cap != 0};
+        v = Variant{blocks > c->lp_grid, c->d.rw && c->d.win, false, c->lpm.lpb && c->d.trace_cap != 0};
         if (v.gs) blocks = c->lp_grid;
     }
     each_kernel<G>([&](RunKernel k, Variant kv) {
@@ -307,208 +262,70 @@ void sh_destroy(tw_shard* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_all(c);
     c->times.destroy();
+    c->st.destroy();
+    c->ex.destroy(c->d);
+    c->sw.destroy();
     if (c->h_active) (void)hipHostFree(c->h_active);
-    if (c->h_st) (void)hipHostFree(c->h_st);
-    if (c->h_win) (void)hipHostFree(c->h_win);
-    if (c->sw.h) (void)hipHostFree(c->sw.h);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
 
-static int validate(const tw_scenario_desc* s) {
-    if (!s || s->abi_version != TW_ABI_VERSION) return TW_ERR_INVALID;
-    if (s->n_replicas == 0 || s->n_nodes == 0 || !s->insns || s->n_insns < TW_PC_USER || s->n_insns > 0xFFFF)
-        return TW_ERR_INVALID;
-    if (s->max_slots < 1 || s->queue_capacity < 1 || s->link_depth < 1 || !s->out_off) return TW_ERR_INVALID;
-    if (s->max_frames > TW_MAX_FRAMES) return TW_ERR_INVALID;
-    if (s->main_pc >= s->n_insns || s->main_node >= s->n_nodes || s->max_timeouts > 65536) return TW_ERR_INVALID;
-    if (s->n_links && (!s->link_dst || !s->link_rev)) return TW_ERR_INVALID;
-    if (s->n_listener_sets && (!s->listener_pc || !s->n_msg_kinds)) return TW_ERR_INVALID;
-    // fixed stubs
-    const uint32_t stub_ops[6] = {TW_OP_WAIT_REG, TW_OP_DELIVER, TW_OP_END, TW_OP_WAIT_REG, TW_OP_TMO_FIRE, TW_OP_END};
-    for (int i = 0; i < 6; ++i)
-        if ((s->insns[i].w0 & 0xFF) != stub_ops[i]) return TW_ERR_INVALID;
-    for (uint32_t l = 0; l < s->n_links; ++l)
-        if (s->link_dst[l] >= s->n_nodes) return TW_ERR_INVALID;
-    if (s->out_off[s->n_nodes] != s->n_links) return TW_ERR_INVALID;
-    return TW_OK;
-}
-
 int sh_reset(tw_shard* c);
 
-// Batch class of every resume pc for the wave kernel (wave.hip PC_*): what the
-// code a thread runs from that pc until its next yield may touch.
-//   1 (LOCAL)   its own record, its own node's vars / binding / out-links, and
-//               forks (whose records and queue entries the batch commit writes);
-//   2 (DELIVER) LOCAL plus the destination node of a delivery (the deliverer stub);
-//   0 (ALONE)   anything that can reach another thread or another node's state
-//               (throwTo, throw, the watchdog's fire, cross-node vars, in-place
-//               handlers): such an event runs as a batch of one.
-// Events in one batch have equal timestamps, consecutive seqs and disjoint node
-// footprints, so running them side by side commits the same effects as
-// TimedT's one-at-a-time loop (TimedT.hs:239-263).  (Sends go over the sender's
-// own out-links, as every lowered scenario's LINK / RLINK links do.)
-static void classify_pcs(const tw_scenario_desc* s, std::vector<uint8_t>& cls) {
-    const uint32_t n = s->n_insns;
-    cls.assign((size_t)n + 1, 0);
-    bool inline_any = false;
-    for (size_t i = 0; i < (size_t)s->n_listener_sets * s->n_msg_kinds; ++i)
-        if (s->listener_pc[i] != TW_PC_NONE && (s->listener_pc[i] & TW_LPC_INLINE)) inline_any = true;
-    std::vector<uint32_t> seen(n, 0xFFFFFFFFu), stk;
-    for (uint32_t p0 = 0; p0 < n; ++p0) {
-        bool alone = false, dlv = false;
-        stk.assign(1, p0);
-        seen[p0] = p0;
-        while (!stk.empty() && !alone) {
-            const uint32_t q = stk.back();
-            stk.pop_back();
-            const uint32_t op = s->insns[q].w0 & 0xFFu;
-            const uint32_t imm = (uint32_t)s->insns[q].imm;
-            uint32_t nx[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
-            switch (op) {
-            case TW_OP_THROW_TO: case TW_OP_THROW: case TW_OP_TMO_FIRE: case TW_OP_NLOADX: case TW_OP_NSTOREX:
-                alone = true;
-                break;
-            case TW_OP_END: case TW_OP_WAIT_REL: case TW_OP_WAIT_ABS: case TW_OP_WAIT_REG: case TW_OP_FORK:
-            case TW_OP_TMO_BEGIN:
-                break;  // the step ends here
-            case TW_OP_DELIVER:
-                if (inline_any) alone = true;
-                dlv = true;
-                nx[0] = q + 1;  // undeliverable: the deliverer goes on
-                break;
-            case TW_OP_JMP:
-                nx[0] = imm;
-                break;
-            case TW_OP_JEQ: case TW_OP_JNE: case TW_OP_JLT: case TW_OP_JLE: case TW_OP_JEQI: case TW_OP_JNEI:
-                nx[0] = imm;
-                nx[1] = q + 1;
-                break;
-            default:
-                if (op >= TW_OP_COUNT) alone = true;
-                nx[0] = q + 1;  // (SEND: a dropped message lets the sender go on)
-                break;
-            }
-            for (uint32_t x : nx) {
-                if (x == 0xFFFFFFFFu) continue;
-                if (x >= n) { alone = true; break; }
-                if (seen[x] != p0) { seen[x] = p0; stk.push_back(x); }
-            }
-        }
-        cls[p0] = alone ? 0 : dlv ? 2 : 1;
-    }
-}
+// ===================================================================== the load
+// load_common's stages; the checks, the batched mode's plan, the
+// classifiers and the geometry choice are load_plan.hpp's.  A stage that
+// fails just returns: load_common's one failure exit frees whatever the load
+// has allocated by then.
+constexpr size_t TW_LDS_LIMIT = 160 * 1024;  // a workgroup's LDS: program + constants must fit beside the queues
+static const LoadLimits LOAD_LIMITS{TW_LIGHT, TW_HEAVY_CAP};
 
-// The handlers a heavy lane's due run may execute data-parallel (tw_lp_due,
-// round 5): the fork_-dispatched handler of a (listener set, kind) whose code,
-// on every path from its entry, touches only its own registers, reads its
-// node's variables, computes out-links and reply links, traces, and sends at
-// most once with END right after the send -- bench/Network's Ping handler
-// `reply Pong` (Receiver/Main.hs:32-38; ForkStrategy fork_, MonadDialog.hs:317).
-// Such a handler's effects are its own (hash terms, counters, one record), so
-// records whose events no other event of the lane interleaves with can run one
-// per thread with the totals of the sequential loop.  Forward jumps only (the
-// walk is bounded by the image); no NSTORE, fork, wait, throw, listen or MYTID.
-static void classify_batch(const tw_scenario_desc* s, std::vector<uint8_t>& bat) {
-    const uint32_t n = s->n_insns, nk = s->n_msg_kinds;
-    bat.assign((size_t)s->n_listener_sets * nk, 0);
-    auto op_at = [&](uint32_t q) { return q < n ? s->insns[q].w0 & 0xFFu : 0xFFu; };
-    std::vector<uint32_t> seen(n, 0xFFFFFFFFu), stk;
-    for (size_t e = 0; e < bat.size(); ++e) {
-        const uint32_t lpc = s->listener_pc[e];
-        if (lpc == TW_PC_NONE || (lpc & TW_LPC_INLINE) || lpc >= n) continue;
-        bool ok = true;
-        stk.assign(1, lpc);
-        seen[lpc] = (uint32_t)e;
-        while (!stk.empty() && ok) {
-            const uint32_t q = stk.back();
-            stk.pop_back();
-            const uint32_t w = s->insns[q].w0, op = w & 0xFFu, b = w >> 16;
-            const uint32_t imm = (uint32_t)s->insns[q].imm;
-            uint32_t nx[2] = {q + 1, 0xFFFFFFFFu};
-            switch (op) {
-            case TW_OP_END: nx[0] = 0xFFFFFFFFu; break;
-            case TW_OP_NOP: case TW_OP_MOV: case TW_OP_ADD: case TW_OP_SUB: case TW_OP_NLOAD: case TW_OP_LINK:
-            case TW_OP_RLINK:
-                break;
-            case TW_OP_SETI: case TW_OP_SETK: case TW_OP_ADDI: case TW_OP_MULI: case TW_OP_NOW: case TW_OP_NODE:
-                ok = !(b & TW_ALU_NSTORE);  // (the fused NSTORE writes a node variable)
-                break;
-            case TW_OP_TRACE:
-                if (b & TW_TRACE_PAIR) nx[0] = q + 2;
-                break;
-            case TW_OP_JMP: case TW_OP_JEQ: case TW_OP_JNE: case TW_OP_JLT: case TW_OP_JLE: case TW_OP_JEQI:
-            case TW_OP_JNEI:
-                ok = imm > q && imm < n;
-                nx[0] = imm;
-                nx[1] = op == TW_OP_JMP ? 0xFFFFFFFFu : q + 1;
-                break;
-            case TW_OP_SEND: {
-                // the send yields 1 µs (it forks the deliverer): the thread must end there
-                const uint32_t k = (b & (TW_SEND_VIA_LINK | TW_SEND_VIA_RLINK)) ? q + 2 : q + 1;
-                ok = op_at(k) == TW_OP_END;
-                nx[0] = 0xFFFFFFFFu;
-                break;
-            }
-            default: ok = false; break;
-            }
-            for (uint32_t x : nx) {
-                if (x == 0xFFFFFFFFu || !ok) continue;
-                if (x >= n) { ok = false; break; }
-                if (seen[x] != (uint32_t)e) { seen[x] = (uint32_t)e; stk.push_back(x); }
-            }
-        }
-        bat[e] = ok ? 1 : 0;
-    }
-}
+// the load's device tables on their way into Dev and tw_shard (null: not in this load)
+struct LoadTabs {
+    uint2* insns = nullptr;
+    int64_t* consts = nullptr;
+    uint32_t *lpc = nullptr, *out_off = nullptr, *ldst = nullptr, *lrev = nullptr, *ltab = nullptr;
+    uint32_t* mbytes = nullptr;
+    uint64_t* lbw = nullptr;
+    uint32_t* iboff = nullptr;
+    uint8_t* phd = nullptr;
+    uint4* ldh = nullptr;
+    int64_t *mregs = nullptr, *nvi = nullptr;
+    uint32_t* lsi = nullptr;
+};
 
-static int load_common(tw_shard* c, const tw_scenario_desc* s, bool lp, uint32_t lp_begin, uint32_t lp_count,
-                       int64_t lookahead, uint32_t inbox_cap, uint32_t outbox_cap, bool lpb = false,
-                       const uint32_t* node_caps = nullptr) {
-    if (!c) return TW_ERR_INVALID;
-    int v = validate(s);
-    if (v) return v;
-    uint32_t rep_lg = 0;
-    if (lpb) {
-        // every replica's nodes as lanes (node-major): a power-of-two replica count
-        while ((1u << rep_lg) < s->n_replicas) ++rep_lg;
-        if ((1u << rep_lg) != s->n_replicas || rep_lg > 16 || (uint64_t)s->n_nodes << rep_lg > 0x7FFFFFFFull ||
-            outbox_cap < 2 || lookahead < 1)
-            return TW_ERR_INVALID;
-        uint64_t tot = 0;
-        for (uint32_t n = 0; n < s->n_nodes; ++n) {
-            const uint32_t k = node_caps ? node_caps[n] : inbox_cap;
-            if (k == 0 || k > TW_HEAVY_CAP) return TW_ERR_INVALID;
-            tot += k;
-        }
-        if ((tot << rep_lg) > 0x7FFFFFFFull) return TW_ERR_INVALID;  // (a lane's inbox base: 31 bits, DW_IB)
-        lp_begin = 0;
-        lp_count = s->n_nodes << rep_lg;
-    } else if (lp && (s->n_replicas != 1 || lp_count == 0 || (uint64_t)lp_begin + lp_count > s->n_nodes ||
-                      inbox_cap == 0 || inbox_cap > TW_LIGHT || outbox_cap == 0 || lookahead < 1)) {
-        return TW_ERR_INVALID;
+// dalloc for a run of allocations: the first failure sticks and ends the run
+struct Alloc {
+    tw_shard* c;
+    int rc = TW_OK;
+    template <class T>
+    void operator()(T*& p, size_t n) {
+        if (rc == TW_OK) rc = dalloc(c, &p, n);
     }
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    free_all(c);
+};
+
+// Stage "describe": the mode, Dev's dimensions, the geometry and its LDS
+// bytes; every instantiation launch_run can pick is told them.
+static int load_describe(tw_shard* c, const tw_scenario_desc* s, const LoadMode& m, const LpbPlan& plan) {
+    const bool lp = m.lp(), lpb = m.lpb();
     Dev& d = c->d;
     d = Dev{};
-    c->lp = lp;
-    c->lpb = lpb;
-    c->n_rep = lpb ? s->n_replicas : 1u;
-    c->heavy_ok = false;
-    c->has_ph1 = false;
-    d.rep_lg = rep_lg;
+    c->lpm.lp = lp;
+    c->lpm.lpb = lpb;
+    c->lpm.n_rep = lpb ? s->n_replicas : 1u;
+    c->lpm.heavy_ok = plan.heavy_ok;
+    c->lpm.has_ph1 = plan.has_ph1;
+    d.rep_lg = m.rep_lg;
     d.lpb = lpb ? 1u : 0u;
-    d.R = lp ? lp_count : s->n_replicas;
+    d.R = lp ? m.lp_count : s->n_replicas;
     d.S = s->max_slots; d.Q = s->queue_capacity;
     d.RQ = lp ? 1u : (uint64_t)d.S * d.R;  // quad stride: LP records contiguous (Lane::hrec)
     d.N = lp ? 1 : s->n_nodes;  // per-lane node arrays
     d.Ntot = s->n_nodes;
-    d.lp0 = lp ? lp_begin : 0;
-    d.IB = inbox_cap;
-    d.out_cap = outbox_cap;
-    d.lookahead = lookahead;
+    d.lp0 = lp ? m.lp_begin : 0;
+    d.IB = lpb ? 0u : m.inbox_cap;  // (batched: per-node caps, Dev::ib_off)
+    d.out_cap = m.outbox_cap;
+    d.lookahead = m.lookahead;
     d.L = s->n_links; d.D = s->link_depth; d.T = s->max_timeouts;
     d.n_insns = s->n_insns; d.n_consts = s->n_consts; d.n_sets = s->n_listener_sets; d.n_kinds = s->n_msg_kinds;
     d.horizon = s->near_horizon_us;
@@ -517,35 +334,22 @@ static int load_common(tw_shard* c, const tw_scenario_desc* s, bool lp, uint32_t
     d.max_frames = s->max_frames ? s->max_frames : 2u;
     d.FXQ = d.max_frames > 2 ? (d.max_frames - 2 + 3) / 4 : 0u;
     d.tie_mode = TW_TIE_FIFO;
+    d.sc_lp = lp ? 1u : 0u;  // LP lanes: one contiguous scalar block per lane (sc_ix)
+    d.has_ph1 = plan.has_ph1 ? 1u : 0u;
+    d.dpar = lp && !plan.has_ph1 ? 1u : 0u;  // (phase-1 lanes drain inside the window: one buffer)
+    d.ib_total = lpb ? plan.ib_entries : (size_t)d.IB * d.R;
     c->tie_flags.assign(d.R, 0u);
-    const size_t R = d.R;
-    const size_t Rt = s->n_replicas;  // replica dimension of the host tables
+    c->main_pc = s->main_pc;
+    c->main_node = s->main_node;
     const size_t prog_lds = 16ull * (d.n_insns + 1) + 8ull * d.n_consts + 4ull * d.n_sets * d.n_kinds;
-    // geometry by replica count (TW_GEOMETRY overrides; LP mode is dense):
-    // <= 4096: a wavefront per replica (C5: 0.32 G events/s vs 0.25 sparse,
-    // 0.20 narrow); < 65536: narrow (C3 at 8192: 2.5 vs 0.99 sparse, 0.74
-    // wave); else dense (one workgroup of 256 per CU)
-    {
-        const char* g = getenv("TW_GEOMETRY");
-        // dense batches of a scenario without far runs (run_capacity 0, e.g.
-        // C2's ping-pong: every event within the near horizon) take the
-        // compact geometry: two waves per SIMD
-        int geo = lp ? TW_GEO_DENSE : R <= 4096 ? TW_GEO_WAVE : R < 65536 ? TW_GEO_NARROW
-                                    : s->run_capacity == 0 ? TW_GEO_COMPACT : TW_GEO_DENSE;
-        const std::pair<const char*, int> names[] = {{"dense", TW_GEO_DENSE}, {"compact", TW_GEO_COMPACT},
-                                                     {"sparse", TW_GEO_SPARSE}, {"half", TW_GEO_HALF},
-                                                     {"wave", TW_GEO_WAVE}, {"narrow", TW_GEO_NARROW}};
-        for (const auto& n : names)
-            if (g && !lp && !strcmp(g, n.first)) geo = n.second;
-        if (geo == TW_GEO_SPARSE && GeoSparse::LDS + prog_lds > 160 * 1024) geo = TW_GEO_DENSE;
-        c->geo = geo;
-    }
+    c->geo = pick_geometry(lp, d.R, s->run_capacity, getenv("TW_GEOMETRY"), GeoSparse::LDS + prog_lds <= TW_LDS_LIMIT);
     const bool wave = c->geo == TW_GEO_WAVE;
     if (c->geo == TW_GEO_COMPACT) d.Cr = 0;  // far events: the HBM heap only
+    if (wave) d.wave_k = (uint32_t)wave_near_k(d.R);
     // (the wave kernel reads the program image through the scalar cache)
     c->lds_bytes = wave ? 0 : with_geo(c, [](auto g) { return g.LDS; }) + prog_lds;
-    if (c->lds_bytes > 160 * 1024) { free_all(c); return TW_ERR_INVALID; }  // program + constants must fit in LDS
-    if (!wave) {  // every instantiation launch_run can pick
+    if (c->lds_bytes > TW_LDS_LIMIT) return TW_ERR_INVALID;
+    if (!wave) {
         hipError_t he = hipSuccess;
         with_geo(c, [&](auto g) {
             each_kernel<decltype(g)>([&](RunKernel k, Variant) {
@@ -556,205 +360,180 @@ static int load_common(tw_shard* c, const tw_scenario_desc* s, bool lp, uint32_t
         });
         HIPCHK(he);
     }
-    int e;
-#define ALLOC(p, n) if ((e = dalloc(c, &p, (n))) != TW_OK) { free_all(c); return e; }
-    uint2* insns; int64_t* consts; uint32_t *lpc, *out_off, *ldst, *lrev, *ltab = nullptr;
-    ALLOC(insns, (size_t)d.n_insns + 1);  // +1 NOP: the fall-through prefetch may read one past
-    ALLOC(consts, d.n_consts);
-    ALLOC(lpc, (size_t)d.n_sets * d.n_kinds);
-    ALLOC(out_off, (size_t)d.Ntot + 1);
-    ALLOC(ldst, d.L);
-    ALLOC(lrev, d.L);
-    if (s->link_table) ALLOC(ltab, (size_t)d.L * d.D * Rt);
-    d.sc_lp = lp ? 1u : 0u;  // LP lanes: one contiguous scalar block per lane (sc_ix)
-    ALLOC(d.scal, (size_t)(lp ? SC_LP_STRIDE : SC_COUNT) * R);
-    ALLOC(d.slots, (size_t)d.S * R * 4);
-    ALLOC(d.free_stk, (size_t)d.S * R);
-    ALLOC(d.far, (size_t)d.Q * R);
-    ALLOC(d.runs, (size_t)(d.Cr ? TW_RUNS * (size_t)d.Cr : 1) * R);
-    if (wave) d.wave_k = (uint32_t)wave_near_k(d.R);
-    ALLOC(d.near_spill, (size_t)(wave ? wave_spill_entries(d.wave_k) : with_geo(c, [](auto g) { return g.SPILL; })) * R);
-    ALLOC(d.dummy, (size_t)TW_DUMMY_REC + R);
-    ALLOC(d.nvars, (size_t)d.N * 4 * R);
-    ALLOC(d.hash, (size_t)d.N * R);
-    ALLOC(d.bind, (size_t)d.N * R);
-    ALLOC(d.bind_own, (size_t)d.N * R);
-    ALLOC(d.bind_rel, (size_t)d.N * R);
-    ALLOC(d.link_ord, (size_t)(d.L ? d.L : 1) * (lp ? (size_t)1 << rep_lg : R));
-    ALLOC(d.tmo_done, (size_t)(d.T ? d.T : 1) * R);
-    ALLOC(d.n_active, 1);
-    ALLOC(c->d_dev, 1);
-    if (d.FXQ) ALLOC(d.fx, (size_t)d.S * R * d.FXQ);
-    uint32_t* mbytes = nullptr;
-    uint64_t* lbw = nullptr;
+    return TW_OK;
+}
+
+// Stage "allocate": every table of the load, in one fixed order
+static int load_alloc(tw_shard* c, const tw_scenario_desc* s, const LoadMode& m, const LpbPlan& plan, LoadTabs& t) {
+    const bool lp = m.lp(), lpb = m.lpb(), wave = c->geo == TW_GEO_WAVE;
+    Dev& d = c->d;
+    const size_t R = d.R;
+    const size_t Rt = s->n_replicas;  // replica dimension of the host tables
+    const uint32_t rep_lg = d.rep_lg;
+    Alloc A{c};
+    A(t.insns, (size_t)d.n_insns + 1);  // +1 NOP: the fall-through prefetch may read one past
+    A(t.consts, d.n_consts);
+    A(t.lpc, (size_t)d.n_sets * d.n_kinds);
+    A(t.out_off, (size_t)d.Ntot + 1);
+    A(t.ldst, d.L);
+    A(t.lrev, d.L);
+    if (s->link_table) A(t.ltab, (size_t)d.L * d.D * Rt);
+    A(d.scal, (size_t)(lp ? SC_LP_STRIDE : SC_COUNT) * R);
+    A(d.slots, (size_t)d.S * R * 4);
+    A(d.free_stk, (size_t)d.S * R);
+    A(d.far, (size_t)d.Q * R);
+    A(d.runs, (size_t)(d.Cr ? TW_RUNS * (size_t)d.Cr : 1) * R);
+    A(d.near_spill, (size_t)(wave ? wave_spill_entries(d.wave_k) : with_geo(c, [](auto g) { return g.SPILL; })) * R);
+    A(d.dummy, (size_t)TW_DUMMY_REC + R);
+    A(d.nvars, (size_t)d.N * 4 * R);
+    A(d.hash, (size_t)d.N * R);
+    A(d.bind, (size_t)d.N * R);
+    A(d.bind_own, (size_t)d.N * R);
+    A(d.bind_rel, (size_t)d.N * R);
+    A(d.link_ord, (size_t)(d.L ? d.L : 1) * (lp ? (size_t)1 << rep_lg : R));
+    A(d.tmo_done, (size_t)(d.T ? d.T : 1) * R);
+    A(d.n_active, 1);
+    A(c->d_dev, 1);
+    if (d.FXQ) A(d.fx, (size_t)d.S * R * d.FXQ);
     if (s->msg_bytes && s->link_bw && d.n_kinds && d.L) {
-        ALLOC(mbytes, d.n_kinds);
-        ALLOC(lbw, d.L);
+        A(t.mbytes, d.n_kinds);
+        A(t.lbw, d.L);
     }
 #ifdef TW_STATS
-    ALLOC(d.prof, 2 * P_COUNT + TW_BPROF);
-    HIPCHK(hipMemsetAsync(d.prof, 0, 8 * (2 * P_COUNT + TW_BPROF), c->stream));
+    A(d.prof, 2 * P_COUNT + TW_BPROF);
 #endif
-    uint32_t* iboff = nullptr;
-    std::vector<uint32_t> h_iboff;
-    uint8_t* phd = nullptr;
-    std::vector<uint8_t> h_ph;
-    if (lpb) {
-        // two-phase windows: a link shorter than the lookahead (over every
-        // replica and ordinal) must run from a phase-0 node into a node that
-        // then runs in phase 1 (after phase 0 has finished the window), and such
-        // a node's inbox must be light (drained at phase 1's first tick)
-        h_ph.assign(s->n_nodes, 0);
-        std::vector<uint8_t> shortl(s->n_links, 0);
-        for (uint32_t l = 0; l < s->n_links; ++l) {
-            uint32_t dmin = 0;
-            if (s->link_table) {
-                dmin = 0x7FFFFFFFu;
-                const uint32_t* e = s->link_table + (size_t)l * s->link_depth * s->n_replicas;
-                for (size_t i = 0; i < (size_t)s->link_depth * s->n_replicas; ++i) {
-                    const uint32_t v = e[i] & 0x7FFFFFFFu;
-                    dmin = v < dmin ? v : dmin;
-                }
-            }
-            if ((int64_t)dmin < lookahead) {
-                shortl[l] = 1;
-                h_ph[s->link_dst[l]] = 1;
-            }
-        }
-        for (uint32_t n = 0; n < s->n_nodes; ++n)
-            for (uint32_t l = s->out_off[n]; l < s->out_off[n + 1]; ++l)
-                if (shortl[l] && h_ph[n]) { free_all(c); return TW_ERR_INVALID; }
-        for (uint32_t n = 0; n < s->n_nodes; ++n) {
-            if (!h_ph[n]) continue;
-            c->has_ph1 = true;
-            if ((node_caps ? node_caps[n] : inbox_cap) > TW_LIGHT) { free_all(c); return TW_ERR_INVALID; }
-        }
-    }
     if (lp) {
-        if (c->has_ph1) {
-            ALLOC(phd, h_ph.size());
-        }
-        size_t ib_entries = (size_t)d.IB * R;
+        if (plan.has_ph1) A(t.phd, plan.phase.size());
+        const size_t ib_entries = d.ib_total;
         if (lpb) {
-            h_iboff.resize((size_t)s->n_nodes + 1);
-            h_iboff[0] = 0;
-            for (uint32_t n = 0; n < s->n_nodes; ++n) {
-                const uint32_t k = node_caps ? node_caps[n] : inbox_cap;
-                h_iboff[n + 1] = h_iboff[n] + k;
-                if (k > TW_LIGHT) c->heavy_ok = true;
-            }
-            ib_entries = (size_t)h_iboff[s->n_nodes] << rep_lg;
-            d.IB = 0;
-            ALLOC(iboff, h_iboff.size());
-            ALLOC(d.spawn, (size_t)TW_SPN * R * 4);
-            ALLOC(d.spawn_n, R);
+            A(t.iboff, plan.ib_off.size());
+            A(d.spawn, (size_t)TW_SPN * R * 4);
+            A(d.spawn_n, R);
         }
-        ALLOC(d.hash_g, (size_t)d.Ntot << rep_lg);
-        ALLOC(d.inbox, ib_entries * 2 * 2);  // two buffers (Dev::dpar)
-        d.ib_total = ib_entries;
-        ALLOC(d.due, c->heavy_ok ? ib_entries * 2 : 2);
-        ALLOC(d.heavy, c->heavy_ok ? 2 * R : 2);
-        ALLOC(d.heavy_n, 2);
-        if (lpb) ALLOC(d.bat_ctr, 2);
-        ALLOC(d.pend_min, 1);
-        ALLOC(d.inbox_n, 2 * R);
-        ALLOC(d.outbox, (size_t)d.out_cap * 2);
-        ALLOC(d.out_n, 1);
-        ALLOC(d.next_t, 1);
-        ALLOC(d.lp_err, 1);
-        ALLOC(d.act, 2 * TW_LP_NB * R);
-        ALLOC(d.act_n, 2 * TW_LP_NB);
-        ALLOC(d.wake, R);
-        ALLOC(d.listed, R);
-        {
-            const size_t nsb = (R + (1u << TW_SUB_LG) - 1) >> TW_SUB_LG;
-            ALLOC(d.sb_mark, nsb);
-            ALLOC(d.sb_scan, nsb);
-            ALLOC(d.sb_min, nsb);
-        }
-        if (lpb) ALLOC(d.inlist, R);
+        A(d.hash_g, (size_t)d.Ntot << rep_lg);
+        A(d.inbox, ib_entries * 2 * 2);  // two buffers (Dev::dpar)
+        A(d.due, plan.heavy_ok ? ib_entries * 2 : 2);
+        A(d.heavy, plan.heavy_ok ? 2 * R : 2);
+        A(d.heavy_n, 2);
+        if (lpb) A(d.bat_ctr, 2);
+        A(d.pend_min, 1);
+        A(d.inbox_n, 2 * R);
+        A(d.outbox, (size_t)d.out_cap * 2);
+        A(d.out_n, 1);
+        A(d.next_t, 1);
+        A(d.lp_err, 1);
+        A(d.act, 2 * TW_LP_NB * R);
+        A(d.act_n, 2 * TW_LP_NB);
+        A(d.wake, R);
+        A(d.listed, R);
+        const size_t nsb = (R + (1u << TW_SUB_LG) - 1) >> TW_SUB_LG;
+        A(d.sb_mark, nsb);
+        A(d.sb_scan, nsb);
+        A(d.sb_min, nsb);
+        if (lpb) A(d.inlist, R);
         // per-replica windows (TW_LPB_GLOBAL=1: one window for the whole batch)
-        d.rw = nullptr;
-        d.cw_min = nullptr;
-        d.cw_mark = nullptr;
         if (lpb && !getenv("TW_LPB_GLOBAL")) {
-            ALLOC(d.rw, (size_t)RW_COUNT << rep_lg);
+            A(d.rw, (size_t)RW_COUNT << rep_lg);
             const size_t nk = ((R >> rep_lg) + (1u << TW_CHUNK_LG) - 1) >> TW_CHUNK_LG;
-            ALLOC(d.cw_min, nk << rep_lg);
-            ALLOC(d.cw_mark, nk << rep_lg);
+            A(d.cw_min, nk << rep_lg);
+            A(d.cw_mark, nk << rep_lg);
         }
-        ALLOC(c->foreign, (size_t)d.out_cap * 2);
-        ALLOC(c->n_foreign, 1);
-        ALLOC(c->staging, (size_t)d.out_cap * 2);
-        ALLOC(c->win_buf, WN_COUNT);  // d.win stays null: the host-driven loop
-        ALLOC(c->red_own, RD_COUNT);
+        A(c->lpm.foreign, (size_t)d.out_cap * 2);
+        A(c->lpm.n_foreign, 1);
+        A(c->lpm.staging, (size_t)d.out_cap * 2);
+        A(c->ex.win_buf, WN_COUNT);  // d.win stays null: the host-driven loop
+        A(c->ex.red_own, RD_COUNT);
     }
-    int64_t *mregs = nullptr, *nvi = nullptr;
-    if (s->main_regs && (!lp || lpb)) ALLOC(mregs, (size_t)s->n_replicas * 4);
-    if (s->node_vars) ALLOC(nvi, (size_t)d.Ntot * 4);
-    uint32_t* lsi = nullptr;
-    if (s->node_listen) ALLOC(lsi, (size_t)d.Ntot);
-#undef ALLOC
+    if (s->main_regs && (!lp || lpb)) A(t.mregs, (size_t)s->n_replicas * 4);
+    if (s->node_vars) A(t.nvi, (size_t)d.Ntot * 4);
+    if (s->node_listen) A(t.lsi, (size_t)d.Ntot);
+    if (lp) A(t.ldh, d.L ? d.L : 1);
+    return A.rc;
+}
+
+// Stage "upload": the descriptor's tables and the plan's into the allocations,
+// their pointers into Dev and the context
+static int load_upload(tw_shard* c, const tw_scenario_desc* s, const LoadMode& m, const LpbPlan& plan,
+                       const LoadTabs& t) {
+    const bool lpb = m.lpb();
+    Dev& d = c->d;
+    const size_t Rt = s->n_replicas;
     hipStream_t st = c->stream;
-    HIPCHK(hipMemsetAsync(insns, 0, sizeof(tw_insn) * (d.n_insns + 1), st));
-    HIPCHK(hipMemcpyAsync(insns, s->insns, sizeof(tw_insn) * d.n_insns, hipMemcpyHostToDevice, st));
-    if (d.n_consts) HIPCHK(hipMemcpyAsync(consts, s->consts, 8 * d.n_consts, hipMemcpyHostToDevice, st));
-    if (d.n_sets) HIPCHK(hipMemcpyAsync(lpc, s->listener_pc, 4ull * d.n_sets * d.n_kinds, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(out_off, s->out_off, 4ull * (d.Ntot + 1), hipMemcpyHostToDevice, st));
+#ifdef TW_STATS
+    HIPCHK(hipMemsetAsync(d.prof, 0, 8 * (2 * P_COUNT + TW_BPROF), st));
+#endif
+    HIPCHK(hipMemsetAsync(t.insns, 0, sizeof(tw_insn) * (d.n_insns + 1), st));
+    HIPCHK(hipMemcpyAsync(t.insns, s->insns, sizeof(tw_insn) * d.n_insns, hipMemcpyHostToDevice, st));
+    if (d.n_consts) HIPCHK(hipMemcpyAsync(t.consts, s->consts, 8 * d.n_consts, hipMemcpyHostToDevice, st));
+    if (d.n_sets) HIPCHK(hipMemcpyAsync(t.lpc, s->listener_pc, 4ull * d.n_sets * d.n_kinds, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(t.out_off, s->out_off, 4ull * (d.Ntot + 1), hipMemcpyHostToDevice, st));
     if (d.L) {
-        HIPCHK(hipMemcpyAsync(ldst, s->link_dst, 4ull * d.L, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(lrev, s->link_rev, 4ull * d.L, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(t.ldst, s->link_dst, 4ull * d.L, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(t.lrev, s->link_rev, 4ull * d.L, hipMemcpyHostToDevice, st));
     }
-    if (ltab) HIPCHK(hipMemcpyAsync(ltab, s->link_table, 4ull * d.L * d.D * Rt, hipMemcpyHostToDevice, st));
-    if (mregs) HIPCHK(hipMemcpyAsync(mregs, s->main_regs, 32ull * s->n_replicas, hipMemcpyHostToDevice, st));
-    if (iboff) HIPCHK(hipMemcpy(iboff, h_iboff.data(), 4 * h_iboff.size(), hipMemcpyHostToDevice));
-    d.ib_off = iboff;
-    if (phd) HIPCHK(hipMemcpy(phd, h_ph.data(), h_ph.size(), hipMemcpyHostToDevice));
-    if (lp) {
+    if (t.ltab) HIPCHK(hipMemcpyAsync(t.ltab, s->link_table, 4ull * d.L * d.D * Rt, hipMemcpyHostToDevice, st));
+    if (t.mregs) HIPCHK(hipMemcpyAsync(t.mregs, s->main_regs, 32ull * s->n_replicas, hipMemcpyHostToDevice, st));
+    if (t.iboff) HIPCHK(hipMemcpy(t.iboff, plan.ib_off.data(), 4 * plan.ib_off.size(), hipMemcpyHostToDevice));
+    if (t.phd) HIPCHK(hipMemcpy(t.phd, plan.phase.data(), plan.phase.size(), hipMemcpyHostToDevice));
+    if (t.ldh) {
         // destination of every link with the heavy bit of its node (a send to a
         // heavy node goes through tw_lp_pack, to a light one straight in)
         std::vector<uint4> h_dh(d.L ? d.L : 1, make_uint4(0, 0, 0, 0));
         for (uint32_t l = 0; l < d.L; ++l) {
             const uint32_t n = s->link_dst[l];
-            const uint32_t cap = lpb ? (node_caps ? node_caps[n] : inbox_cap) : d.IB;
+            const uint32_t cap = lpb ? m.cap(n) : d.IB;
             const bool heavy = lpb && cap > TW_LIGHT;
-            h_dh[l] = make_uint4(n | (heavy ? 0x80000000u : 0u), lpb ? h_iboff[n] : 0u, cap, 0u);
+            h_dh[l] = make_uint4(n | (heavy ? 0x80000000u : 0u), lpb ? plan.ib_off[n] : 0u, cap, 0u);
         }
-        uint4* ldh = nullptr;
-        if ((e = dalloc(c, &ldh, h_dh.size())) != TW_OK) { free_all(c); return e; }
-        HIPCHK(hipMemcpy(ldh, h_dh.data(), 16 * h_dh.size(), hipMemcpyHostToDevice));
-        d.link_dsth = ldh;
-        d.dpar = c->has_ph1 ? 0u : 1u;  // (phase-1 lanes drain inside the window: one buffer)
+        HIPCHK(hipMemcpy(t.ldh, h_dh.data(), 16 * h_dh.size(), hipMemcpyHostToDevice));
     }
-    d.phase = phd;
-    d.has_ph1 = c->has_ph1 ? 1u : 0u;
-    if (nvi) HIPCHK(hipMemcpyAsync(nvi, s->node_vars, 32ull * d.Ntot, hipMemcpyHostToDevice, st));
-    if (lsi) HIPCHK(hipMemcpyAsync(lsi, s->node_listen, 4ull * d.Ntot, hipMemcpyHostToDevice, st));
-    if (mbytes) {
-        HIPCHK(hipMemcpyAsync(mbytes, s->msg_bytes, 4ull * d.n_kinds, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(lbw, s->link_bw, 8ull * d.L, hipMemcpyHostToDevice, st));
+    if (t.nvi) HIPCHK(hipMemcpyAsync(t.nvi, s->node_vars, 32ull * d.Ntot, hipMemcpyHostToDevice, st));
+    if (t.lsi) HIPCHK(hipMemcpyAsync(t.lsi, s->node_listen, 4ull * d.Ntot, hipMemcpyHostToDevice, st));
+    if (t.mbytes) {
+        HIPCHK(hipMemcpyAsync(t.mbytes, s->msg_bytes, 4ull * d.n_kinds, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(t.lbw, s->link_bw, 8ull * d.L, hipMemcpyHostToDevice, st));
     }
-    d.msg_bytes = mbytes;
-    d.link_bw = lbw;
-    if (wave) {
+    d.insns = t.insns; d.consts = t.consts; d.lpc = t.lpc; d.out_off = t.out_off; d.link_dst = t.ldst; d.link_rev = t.lrev;
+    d.link_table = t.ltab;
+    d.ib_off = t.iboff;
+    d.phase = t.phd;
+    d.link_dsth = t.ldh;
+    d.msg_bytes = t.mbytes;
+    d.link_bw = t.lbw;
+    c->main_regs = t.mregs;
+    c->nv_init = t.nvi;
+    c->listen_init = t.lsi;
+    return TW_OK;
+}
+
+// a classifier's bytes as a device table
+static int upload_bytes(tw_shard* c, const std::vector<uint8_t>& h, const uint8_t** out) {
+    uint8_t* p = nullptr;
+    int e = dalloc(c, &p, h.size());
+    if (e) return e;
+    HIPCHK(hipMemcpy(p, h.data(), h.size(), hipMemcpyHostToDevice));
+    *out = p;
+    return TW_OK;
+}
+
+// Stage "feature tables": the wave kernel's pc classes, tw_lp_due's batchable
+// handlers, the sweeps' kill stubs, the prefix's T0
+static int load_features(tw_shard* c, const tw_scenario_desc* s, const LoadMode& m) {
+    Dev& d = c->d;
+    if (c->geo == TW_GEO_WAVE) {
         std::vector<uint8_t> cls;
         classify_pcs(s, cls);
-        uint8_t* pcl = nullptr;
-        if ((e = dalloc(c, &pcl, cls.size())) != TW_OK) { free_all(c); return e; }
-        HIPCHK(hipMemcpy(pcl, cls.data(), cls.size(), hipMemcpyHostToDevice));
-        d.pc_cls = pcl;
+        int e = upload_bytes(c, cls, &d.pc_cls);
+        if (e) return e;
     }
-    d.lpc_bat = nullptr;
-    if (lpb && !c->has_ph1 && d.D == 1 && d.n_sets && !(getenv("TW_LP_BATCH") && getenv("TW_LP_BATCH")[0] == '0')) {
+    if (m.lpb() && !c->lpm.has_ph1 && d.D == 1 && d.n_sets && !(getenv("TW_LP_BATCH") && getenv("TW_LP_BATCH")[0] == '0')) {
         std::vector<uint8_t> bat;
         classify_batch(s, bat);
         bool any = false;
         for (uint8_t x : bat) any = any || x;
         if (any) {
-            uint8_t* bd = nullptr;
-            if ((e = dalloc(c, &bd, bat.size())) != TW_OK) { free_all(c); return e; }
-            HIPCHK(hipMemcpy(bd, bat.data(), bat.size(), hipMemcpyHostToDevice));
-            d.lpc_bat = bd;
+            int e = upload_bytes(c, bat, &d.lpc_bat);
+            if (e) return e;
         }
     }
     if (far_run_geo(c) && d.Cr) {
@@ -768,7 +547,7 @@ static int load_common(tw_shard* c, const tw_scenario_desc* s, bool lp, uint32_t
             dalloc(c, &stub, plan.stub.size()) == TW_OK && dalloc(c, &acc, sweep_acc_words(d.R)) == TW_OK &&
             dalloc(c, &stats, SWS_COUNT) == TW_OK) {
             HIPCHK(hipMemcpy(stub, plan.stub.data(), 4 * plan.stub.size(), hipMemcpyHostToDevice));
-            HIPCHK(hipMemsetAsync(stats, 0, 8 * SWS_COUNT, st));
+            HIPCHK(hipMemsetAsync(stats, 0, 8 * SWS_COUNT, c->stream));
             c->sw.tab.stub = stub;
             c->sw.tab.acc = acc;
             c->sw.tab.stats = stats;
@@ -780,34 +559,63 @@ static int load_common(tw_shard* c, const tw_scenario_desc* s, bool lp, uint32_t
         }
     }
     // the send-free prefix (prefix_classify.hpp): replica contexts only
-    c->px.t0 = lp ? 0 : prefix_t0(s->insns, s->n_insns, s->consts, s->n_consts, s->main_pc);
+    c->px.t0 = m.lp() ? 0 : prefix_t0(s->insns, s->n_insns, s->consts, s->n_consts, s->main_pc);
     // (an image that never sends ends inside its prefix: the pilot would run the
     // first workgroup's replicas to the end, without sweeps, and be refused)
     if (c->px.t0 == INT64_MAX) c->px.t0 = 0;
-    d.insns = insns; d.consts = consts; d.lpc = lpc; d.out_off = out_off; d.link_dst = ldst; d.link_rev = lrev;
-    d.link_table = ltab;
-    c->main_pc = s->main_pc;
-    c->main_node = s->main_node;
-    c->main_regs = mregs;
-    c->nv_init = nvi;
-    c->listen_init = lsi;
-    c->loaded = true;
-    int rc = sh_reset(c);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(st));
     return TW_OK;
 }
 
-int sh_load(tw_shard* c, const tw_scenario_desc* s) { return load_common(c, s, false, 0, 0, 0, 0, 0); }
+// the stages behind the unload
+static int load_stages(tw_shard* c, const tw_scenario_desc* s, const LoadMode& m, const LpbPlan& plan) {
+    if (plan.status) return plan.status;
+    LoadTabs t;
+    int rc = load_describe(c, s, m, plan);
+    if (!rc) rc = load_alloc(c, s, m, plan, t);
+    if (!rc) rc = load_upload(c, s, m, plan, t);
+    if (!rc) rc = load_features(c, s, m);
+    if (rc) return rc;
+    c->loaded = true;
+    rc = sh_reset(c);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return TW_OK;
+}
+
+// A refusal of the descriptor or of the mode's arguments leaves the previous
+// load as it is; from the unload on, every failure leaves the context unloaded.
+static int load_common(tw_shard* c, const tw_scenario_desc* s, LoadMode m) {
+    if (!c) return TW_ERR_INVALID;
+    int v = validate(s);
+    if (!v) v = load_mode_check(s, m, LOAD_LIMITS);
+    if (v) return v;
+    const LpbPlan plan = m.lpb() ? lpb_plan(s, m, LOAD_LIMITS) : LpbPlan{};
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    free_all(c);
+    const int rc = load_stages(c, s, m, plan);
+    if (rc) free_all(c);
+    return rc;
+}
+
+int sh_load(tw_shard* c, const tw_scenario_desc* s) { return load_common(c, s, LoadMode{}); }
 
 int sh_lp_load(tw_shard* c, const tw_scenario_desc* s, uint32_t lp_begin, uint32_t lp_count, int64_t lookahead_us,
                uint32_t inbox_cap, uint32_t outbox_cap) {
-    return load_common(c, s, true, lp_begin, lp_count, lookahead_us, inbox_cap, outbox_cap);
+    LoadMode m;
+    m.kind = LoadMode::NODES;
+    m.lp_begin = lp_begin; m.lp_count = lp_count;
+    m.lookahead = lookahead_us; m.inbox_cap = inbox_cap; m.outbox_cap = outbox_cap;
+    return load_common(c, s, m);
 }
 
 int sh_lpb_load(tw_shard* c, const tw_scenario_desc* s, int64_t lookahead_us, const uint32_t* node_inbox_cap,
                 uint32_t inbox_cap, uint32_t outbox_cap) {
-    return load_common(c, s, true, 0, 0, lookahead_us, inbox_cap, outbox_cap, true, node_inbox_cap);
+    LoadMode m;
+    m.kind = LoadMode::BATCHED;
+    m.lookahead = lookahead_us; m.inbox_cap = inbox_cap; m.outbox_cap = outbox_cap;
+    m.node_caps = node_inbox_cap;
+    return load_common(c, s, m);
 }
 
 int sh_reset(tw_shard* c) {
@@ -821,22 +629,22 @@ int sh_reset(tw_shard* c) {
     HIPCHK(hipMemsetAsync(d.nvars, 0, 32ull * d.N * R, st));
     HIPCHK(hipMemsetAsync(d.hash, 0, 8ull * d.N * R, st));
     HIPCHK(hipMemsetAsync(d.bind, 0, 4ull * d.N * R, st));
-    HIPCHK(hipMemsetAsync(d.link_ord, 0, 4ull * (d.L ? d.L : 1) * (c->lp ? (size_t)1 << d.rep_lg : R), st));
+    HIPCHK(hipMemsetAsync(d.link_ord, 0, 4ull * (d.L ? d.L : 1) * (c->lpm.lp ? (size_t)1 << d.rep_lg : R), st));
     HIPCHK(hipMemsetAsync(d.tmo_done, 0, (size_t)(d.T ? d.T : 1) * R, st));
-    if (c->lp) {
+    if (c->lpm.lp) {
         HIPCHK(hipMemsetAsync(d.hash_g, 0, 8ull * ((size_t)d.Ntot << d.rep_lg), st));
         HIPCHK(hipMemsetAsync(d.heavy_n, 0, 8, st));
         if (d.bat_ctr) HIPCHK(hipMemsetAsync(d.bat_ctr, 0, 16, st));
-        if (d.trace_n) HIPCHK(hipMemsetAsync(d.trace_n, 0, 8ull * c->n_rep, st));
+        if (d.trace_n) HIPCHK(hipMemsetAsync(d.trace_n, 0, 8ull * c->lpm.n_rep, st));
         if (d.inlist) HIPCHK(hipMemsetAsync(d.inlist, 0, 4ull * R, st));
         HIPCHK(hipMemsetAsync(d.pend_min, 0xFF, 8, st));
         HIPCHK(hipMemsetAsync(d.out_n, 0, 4, st));
         HIPCHK(hipMemsetAsync(d.lp_err, 0, 4, st));
-        HIPCHK(hipMemsetAsync(c->n_foreign, 0, 4, st));
+        HIPCHK(hipMemsetAsync(c->lpm.n_foreign, 0, 4, st));
         c->d.act_cur = 0;
         c->d.wid = 0;
         HIPCHK(hipMemsetAsync(d.act_n, 0, 8 * TW_LP_NB, st));
-        c->lpb_fresh = c->lpb;
+        c->lpm.fresh = c->lpm.lpb;
     }
     if (d.pq_hdr) {
         // empty MinQueues: no element, no node used, every rank a Skip
@@ -849,7 +657,7 @@ int sh_reset(tw_shard* c) {
     uint32_t blocks = (uint32_t)((R + TW_WG - 1) / TW_WG);
     hipLaunchKernelGGL(tw_init_kernel, dim3(blocks), dim3(TW_WG), 0, st, d, c->main_pc, c->main_node,
                        (const int64_t*)c->main_regs, (const int64_t*)c->nv_init, (const uint32_t*)c->listen_init,
-                       c->lp ? 1 : 0, c->seq0, c->tid0);
+                       c->lpm.lp ? 1 : 0, c->seq0, c->tid0);
     HIPCHK(hipGetLastError());
     c->px.fresh = true;
     return TW_OK;
@@ -887,7 +695,7 @@ static int run_round(tw_shard* c, int n, int64_t t_end, uint64_t limit, uint32_t
     const Prefix::Snap::Clean& cl = c->px.snap.clean;
     for (int i = 0; i < n; ++i) {
         HIPCHK(hipMemsetAsync(d.n_active, 0, 4, st));
-        if (c->lp) HIPCHK(hipMemsetAsync(d.next_t, 0xFF, 8, st));
+        if (c->lpm.lp) HIPCHK(hipMemsetAsync(d.next_t, 0xFF, 8, st));
         int rc = c->times.timed(st, [&]() -> int { return launch_event(c, st, t_end, limit, budget, grid); });
         if (rc) return rc;
         ++*launches;
@@ -1062,13 +870,13 @@ static int reduce_stats(tw_shard* c, uint32_t launches, std::chrono::steady_cloc
     const Dev& d = c->d;
     hipStream_t st = c->stream;
     std::memset(out, 0, sizeof(*out));
-    HIPCHK(hipMemsetAsync(c->st_out, 0, 64, st));
+    HIPCHK(hipMemsetAsync(c->st.out, 0, 64, st));
     hipLaunchKernelGGL(tw_stats_kernel, dim3((uint32_t)((d.R + 255) / 256)), dim3(256), 0, st, d,
-                       (const uint64_t*)c->st_ev0, c->st_out);
+                       (const uint64_t*)c->st.ev0, c->st.out);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_st, c->st_out, 64, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(c->st.h, c->st.out, 64, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    const unsigned long long* h = c->h_st;
+    const unsigned long long* h = c->st.h;
     out->events = h[0];
     out->delivered = h[1];
     out->dropped = h[2];
@@ -1099,7 +907,7 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
     if (was_fresh) c->px.chain = false;
     c->px.rows_skipped = c->px.bytes_stored = 0;
     c->px.audited = false;
-    if (c->lpb) {
+    if (c->lpm.lpb) {
         // the batched window loop runs every replica to quiescence
         if (t_end_us != INT64_MAX || max_events != UINT64_MAX) return TW_ERR_INVALID;
         return lpb_run(c, out);
@@ -1113,19 +921,19 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
     // (a device-side copy of the events column; tw_stats_kernel reduces the
     // run's statistics on the device at the end)
     if (out) {
-        if (!c->st_ev0) HIPCHK(hipMalloc((void**)&c->st_ev0, 8ull * (d.R ? d.R : 1)));
-        if (!c->st_out) HIPCHK(hipMalloc((void**)&c->st_out, 64));
-        if (!c->h_st) HIPCHK(hipHostMalloc((void**)&c->h_st, 64));
+        if (!c->st.ev0) HIPCHK(hipMalloc((void**)&c->st.ev0, 8ull * (d.R ? d.R : 1)));
+        if (!c->st.out) HIPCHK(hipMalloc((void**)&c->st.out, 64));
+        if (!c->st.h) HIPCHK(hipHostMalloc((void**)&c->st.h, 64));
         if (d.sc_lp)  // (the events word of every lane's block: one strided copy)
-            HIPCHK(hipMemcpy2DAsync(c->st_ev0, 8, d.scal + SC_EVENTS, 8ull * SC_LP_STRIDE, 8, d.R,
+            HIPCHK(hipMemcpy2DAsync(c->st.ev0, 8, d.scal + SC_EVENTS, 8ull * SC_LP_STRIDE, 8, d.R,
                                     hipMemcpyDeviceToDevice, st));
         else
-            HIPCHK(hipMemcpyAsync(c->st_ev0, d.scal + (size_t)SC_EVENTS * d.R, 8ull * d.R, hipMemcpyDeviceToDevice,
+            HIPCHK(hipMemcpyAsync(c->st.ev0, d.scal + (size_t)SC_EVENTS * d.R, 8ull * d.R, hipMemcpyDeviceToDevice,
                                   st));
     }
     const uint64_t limit = max_events;  // cumulative per-replica cap
     c->times.start();
-    if (c->lp) {
+    if (c->lpm.lp) {
         // a new window: serve the list built since the last call (nodes with a
         // live thread or new records); start an empty one for the next call
         c->d.act_cur ^= 1u;
@@ -1142,7 +950,7 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
     }();
     // launches between host checks: a replica run needs several budgets; an LP
     // window is almost always done after one launch
-    const int per_check = c->lp ? 1 : 4;
+    const int per_check = c->lpm.lp ? 1 : 4;
     uint32_t launches = 0;
     const bool swept_order = far_run_geo(c) && ordered_ties(c);
     // the send-free prefix: a fresh replica run that reaches T0 - 1
@@ -1215,10 +1023,10 @@ int sh_read_results(tw_shard* c, tw_replica_result* out, size_t n) {
     if (!c || !out) return TW_ERR_INVALID;
     if (!c->loaded) return TW_ERR_STATE;
     const Dev& d = c->d;
-    if (n < (c->lpb ? c->n_rep : d.R)) return TW_ERR_INVALID;
+    if (n < (c->lpm.lpb ? c->lpm.n_rep : d.R)) return TW_ERR_INVALID;
     HIPCHK(hipSetDevice(c->device));
-    if (c->lpb) {
-        const uint32_t nr = c->n_rep;
+    if (c->lpm.lpb) {
+        const uint32_t nr = c->lpm.n_rep;
         uint64_t* dd = nullptr;
         HIPCHK(hipMallocAsync((void**)&dd, 64ull * nr, c->stream));
         HIPCHK(hipMemsetAsync(dd, 0, 64ull * nr, c->stream));
@@ -1270,7 +1078,7 @@ static int digest(tw_shard* c, std::vector<uint64_t>& h) {
 int sh_tie_audit(tw_shard* c, int64_t t_end_us, uint64_t max_events, uint32_t probes, tw_stats* out) {
     if (!c) return TW_ERR_INVALID;
     if (!c->loaded) return TW_ERR_STATE;
-    if (c->lp || probes < 1 || probes > 2) return TW_ERR_INVALID;
+    if (c->lpm.lp || probes < 1 || probes > 2) return TW_ERR_INVALID;
     HIPCHK(hipSetDevice(c->device));
     std::vector<std::vector<uint64_t>> dg(probes + 1);
     int rc = TW_OK;
@@ -1295,7 +1103,7 @@ int sh_tie_audit(tw_shard* c, int64_t t_end_us, uint64_t max_events, uint32_t pr
 int sh_geometry(tw_shard* c) {
     if (!c) return TW_ERR_INVALID;
     if (!c->loaded) return TW_ERR_STATE;
-    return c->lpb ? TW_GEO_LPB : c->lp ? TW_GEO_LP : c->geo;
+    return c->lpm.lpb ? TW_GEO_LPB : c->lpm.lp ? TW_GEO_LP : c->geo;
 }
 
 // The equal-timestamp order of later runs (include/timewarp.h tw_set_tie_mode).
@@ -1308,9 +1116,9 @@ int sh_set_tie_mode(tw_shard* c, uint32_t mode) {
     if (mode > TW_TIE_FORKFIRST) return TW_ERR_INVALID;
     // a forked child first: the lane-per-replica kernels (their fork_in_place);
     // the wave and logical-process kernels keep the other orders
-    if (mode == TW_TIE_FORKFIRST && (c->lp || c->geo == TW_GEO_WAVE)) return TW_ERR_INVALID;
+    if (mode == TW_TIE_FORKFIRST && (c->lpm.lp || c->geo == TW_GEO_WAVE)) return TW_ERR_INVALID;
     if (mode == TW_TIE_PQUEUE) {
-        if (c->lp || c->geo != TW_GEO_WAVE) return TW_ERR_INVALID;  // the wave kernel only
+        if (c->lpm.lp || c->geo != TW_GEO_WAVE) return TW_ERR_INVALID;  // the wave kernel only
         HIPCHK(hipSetDevice(c->device));
         HIPCHK(hipStreamSynchronize(c->stream));
         Dev& d = c->d;
@@ -1411,12 +1219,12 @@ int sh_read_hashes(tw_shard* c, uint64_t* out, size_t n) {
     const Dev& d = c->d;
     if (n < (size_t)d.R * d.N) return TW_ERR_INVALID;
     HIPCHK(hipSetDevice(c->device));
-    if (c->lpb) {  // hash_g is [node][replica] over the batch too
+    if (c->lpm.lpb) {  // hash_g is [node][replica] over the batch too
         std::vector<uint64_t> tmp((size_t)d.Ntot << d.rep_lg);
         HIPCHK(hipMemcpyAsync(tmp.data(), d.hash_g, 8 * tmp.size(), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         for (uint32_t node = 0; node < d.Ntot; ++node)
-            for (uint32_t q = 0; q < c->n_rep; ++q) out[(size_t)q * d.Ntot + node] = tmp[((size_t)node << d.rep_lg) | q];
+            for (uint32_t q = 0; q < c->lpm.n_rep; ++q) out[(size_t)q * d.Ntot + node] = tmp[((size_t)node << d.rep_lg) | q];
         return TW_OK;
     }
     std::vector<uint64_t> tmp((size_t)d.R * d.N);  // device layout [node][replica]
@@ -1432,14 +1240,14 @@ static int lp_scatter(tw_shard* c, const uint4* recs, uint32_t n, bool to_foreig
     if (n == 0) return TW_OK;
     uint32_t blocks = (n + 255) / 256;
     hipLaunchKernelGGL(tw_lp_scatter, dim3(blocks), dim3(256), 0, c->stream, d, recs, n,
-                       to_foreign ? c->foreign : nullptr, c->n_foreign, d.out_cap);
+                       to_foreign ? c->lpm.foreign : nullptr, c->lpm.n_foreign, d.out_cap);
     HIPCHK(hipGetLastError());
     return TW_OK;
 }
 
 int sh_lp_window(tw_shard* c, int64_t t_end_excl, int64_t* next_t, uint64_t* n_foreign) {
     if (!c || !next_t) return TW_ERR_INVALID;
-    if (!c->loaded || !c->lp) return TW_ERR_STATE;
+    if (!c->loaded || !c->lpm.lp) return TW_ERR_STATE;
     tw_stats st{};
     int rc = sh_run(c, t_end_excl - 1, UINT64_MAX, nullptr);
     if (rc) return rc;
@@ -1456,7 +1264,7 @@ int sh_lp_window(tw_shard* c, int64_t t_end_excl, int64_t* next_t, uint64_t* n_f
     uint64_t nt = 0;
     uint32_t nf = 0, err = 0;
     HIPCHK(hipMemcpyAsync(&nt, d.next_t, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&nf, c->n_foreign, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&nf, c->lpm.n_foreign, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&err, d.lp_err, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (err) return TW_ERR_REPLICA;
@@ -1467,14 +1275,14 @@ int sh_lp_window(tw_shard* c, int64_t t_end_excl, int64_t* next_t, uint64_t* n_f
 
 int sh_lp_take_outbox(tw_shard* c, tw_lp_record* out, size_t cap, size_t* n) {
     if (!c || !n) return TW_ERR_INVALID;
-    if (!c->loaded || !c->lp) return TW_ERR_STATE;
+    if (!c->loaded || !c->lpm.lp) return TW_ERR_STATE;
     hipStream_t s = c->stream;
     uint32_t nf = 0;
-    HIPCHK(hipMemcpyAsync(&nf, c->n_foreign, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&nf, c->lpm.n_foreign, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (nf > cap || !out) { *n = nf; return nf > cap ? TW_ERR_INVALID : TW_OK; }
-    if (nf) HIPCHK(hipMemcpyAsync(out, c->foreign, 32ull * nf, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemsetAsync(c->n_foreign, 0, 4, s));
+    if (nf) HIPCHK(hipMemcpyAsync(out, c->lpm.foreign, 32ull * nf, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemsetAsync(c->lpm.n_foreign, 0, 4, s));
     HIPCHK(hipStreamSynchronize(s));
     *n = nf;
     return TW_OK;
@@ -1482,13 +1290,13 @@ int sh_lp_take_outbox(tw_shard* c, tw_lp_record* out, size_t cap, size_t* n) {
 
 int sh_lp_inject(tw_shard* c, const tw_lp_record* recs, size_t n, int64_t* next_t) {
     if (!c || (n && !recs)) return TW_ERR_INVALID;
-    if (!c->loaded || !c->lp) return TW_ERR_STATE;
+    if (!c->loaded || !c->lpm.lp) return TW_ERR_STATE;
     const Dev& d = c->d;
     if (n > d.out_cap) return TW_ERR_INVALID;
     hipStream_t s = c->stream;
     if (n) {
-        HIPCHK(hipMemcpyAsync(c->staging, recs, 32ull * n, hipMemcpyHostToDevice, s));
-        int rc = lp_scatter(c, c->staging, (uint32_t)n, false);
+        HIPCHK(hipMemcpyAsync(c->lpm.staging, recs, 32ull * n, hipMemcpyHostToDevice, s));
+        int rc = lp_scatter(c, c->lpm.staging, (uint32_t)n, false);
         if (rc) return rc;
     }
     uint64_t nt = 0;
@@ -1503,7 +1311,7 @@ int sh_lp_inject(tw_shard* c, const tw_lp_record* recs, size_t n, int64_t* next_
 
 int sh_lp_results(tw_shard* c, tw_replica_result* agg, uint64_t* node_hashes, size_t n_nodes) {
     if (!c || !agg) return TW_ERR_INVALID;
-    if (!c->loaded || !c->lp) return TW_ERR_STATE;
+    if (!c->loaded || !c->lpm.lp) return TW_ERR_STATE;
     const Dev& d = c->d;
     std::vector<tw_replica_result> rr(d.R);
     int rc = sh_read_results(c, rr.data(), rr.size());
@@ -1540,36 +1348,28 @@ int sh_set_stream(tw_shard* c, void* hs) {
 // carry buffer (records beyond a tick's block size wait there).
 static int exchange_common(tw_shard* c, uint32_t world, uint32_t rank, const uint32_t* starts, uint32_t cap) {
     if (!c || world == 0 || rank >= world || !starts) return TW_ERR_INVALID;
-    if (!c->loaded || !c->lp) return TW_ERR_STATE;
+    if (!c->loaded || !c->lpm.lp) return TW_ERR_STATE;
     if (world > 1 && cap == 0) return TW_ERR_INVALID;
     for (uint32_t g = 0; g < world; ++g)
         if (starts[g] > starts[g + 1]) return TW_ERR_INVALID;
     if (starts[rank] != c->d.lp0 || starts[rank + 1] != c->d.lp0 + c->d.R) return TW_ERR_INVALID;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->ex_starts) HIPCHK(hipFree(c->ex_starts));
-    if (c->ex_carry) HIPCHK(hipFree(c->ex_carry));
-    c->ex_starts = nullptr;
-    c->ex_carry = nullptr;
-    c->d.carry = nullptr;
-    c->d.carry_n = nullptr;
-    c->d.carry_cap = 0;
-    HIPCHK(hipMalloc((void**)&c->ex_starts, 4ull * (world + 1)));
-    HIPCHK(hipMemcpy(c->ex_starts, starts, 4ull * (world + 1), hipMemcpyHostToDevice));
+    c->ex.drop(c->d);
+    HIPCHK(hipMalloc((void**)&c->ex.starts, 4ull * (world + 1)));
+    HIPCHK(hipMemcpy(c->ex.starts, starts, 4ull * (world + 1), hipMemcpyHostToDevice));
     if (world > 1) {
         // a tick's foreign records beyond the block size: at most a tick's outbox
         const uint32_t cc = c->d.out_cap < (1u << 20) ? c->d.out_cap : (1u << 20);
         const size_t bytes = 2ull * cc * 32 + 256;
-        HIPCHK(hipMalloc(&c->ex_carry, bytes));
-        HIPCHK(hipMemsetAsync(c->ex_carry, 0, bytes, c->stream));
-        c->d.carry_n = (uint32_t*)c->ex_carry;
-        c->d.carry = (uint4*)((char*)c->ex_carry + 256);
-        c->d.carry_cap = cc;
+        HIPCHK(hipMalloc(&c->ex.carry, bytes));
+        HIPCHK(hipMemsetAsync(c->ex.carry, 0, bytes, c->stream));
+        c->ex.set_carry(c->d, cc);
     }
-    c->ex_world = world;
-    c->ex_rank = rank;
-    c->ex_cap = cap;
-    c->ex_cap_eff = c->ex_cap;
+    c->ex.world = world;
+    c->ex.rank = rank;
+    c->ex.cap = cap;
+    c->ex.cap_eff = c->ex.cap;
     return TW_OK;
 }
 
@@ -1578,11 +1378,9 @@ int sh_lp_exchange_setup(tw_shard* c, uint32_t world, uint32_t rank, const uint3
     if (c && world > 1 && (!send || !recv || !red)) return TW_ERR_INVALID;
     int rc = exchange_common(c, world, rank, starts, cap);
     if (rc) return rc;
-    if (c->ex_own) HIPCHK(hipFree(c->ex_own));
-    c->ex_own = nullptr;
-    c->ex_send = world > 1 ? (uint4*)send : nullptr;
-    c->ex_recv = world > 1 ? (uint4*)recv : nullptr;
-    c->ex_red = world > 1 ? red : c->red_own;
+    c->ex.send = world > 1 ? (uint4*)send : nullptr;
+    c->ex.recv = world > 1 ? (uint4*)recv : nullptr;
+    c->ex.red = world > 1 ? red : c->ex.red_own;
     if (world > 1) HIPCHK(hipMemsetAsync(send, 0, 32ull * world * (cap + 1), c->stream));
     return TW_OK;
 }
@@ -1592,40 +1390,38 @@ int sh_lp_exchange_setup(tw_shard* c, uint32_t world, uint32_t rank, const uint3
 int sh_lp_exchange_own(tw_shard* c, uint32_t world, uint32_t rank, const uint32_t* starts, uint32_t cap) {
     int rc = exchange_common(c, world, rank, starts, world > 1 ? cap : 1u);
     if (rc) return rc;
-    if (c->ex_own) HIPCHK(hipFree(c->ex_own));
-    c->ex_own = nullptr;
-    const size_t blk = 32ull * world * ((size_t)c->ex_cap + 1);
-    HIPCHK(hipMalloc(&c->ex_own, 2 * blk + 8ull * RD_COUNT));
-    HIPCHK(hipMemsetAsync(c->ex_own, 0, 2 * blk + 8ull * RD_COUNT, c->stream));
+    const size_t blk = 32ull * world * ((size_t)c->ex.cap + 1);
+    HIPCHK(hipMalloc(&c->ex.own, 2 * blk + 8ull * RD_COUNT));
+    HIPCHK(hipMemsetAsync(c->ex.own, 0, 2 * blk + 8ull * RD_COUNT, c->stream));
     // (one rank too: its import, fill and the all-reduce of the words then go
     // through the transport -- a one-rank RCCL communicator -- like any rank's)
-    c->ex_send = (uint4*)c->ex_own;
-    c->ex_recv = (uint4*)((char*)c->ex_own + blk);
-    c->ex_red = (int64_t*)((char*)c->ex_own + 2 * blk);
+    c->ex.send = (uint4*)c->ex.own;
+    c->ex.recv = (uint4*)((char*)c->ex.own + blk);
+    c->ex.red = (int64_t*)((char*)c->ex.own + 2 * blk);
     return TW_OK;
 }
 
 void sh_lp_exchange_info(tw_shard* c, ShardXchg* x) {
     x->device = c->device;
     x->stream = c->stream;
-    x->send = c->ex_send;
-    x->recv = c->ex_recv;
-    x->red = c->ex_red;
-    x->world = c->ex_world;
-    x->stride = c->ex_cap;
-    x->cap_eff = c->ex_cap_eff;
+    x->send = c->ex.send;
+    x->recv = c->ex.recv;
+    x->red = c->ex.red;
+    x->world = c->ex.world;
+    x->stride = c->ex.cap;
+    x->cap_eff = c->ex.cap_eff;
 }
 int sh_lp_set_block(tw_shard* c, uint32_t cap_eff) {
-    if (!c || cap_eff == 0 || cap_eff > c->ex_cap) return TW_ERR_INVALID;
-    c->ex_cap_eff = cap_eff;
+    if (!c || cap_eff == 0 || cap_eff > c->ex.cap) return TW_ERR_INVALID;
+    c->ex.cap_eff = cap_eff;
     return TW_OK;
 }
 // WN_XMAX after a tw_lp_progress (the largest per-rank demand of one tick since
 // the last clear); clear it on the device (stream-ordered)
-int64_t sh_lp_xmax(tw_shard* c) { return c->h_win ? c->h_win[WN_XMAX] : 0; }
+int64_t sh_lp_xmax(tw_shard* c) { return c->ex.h_win ? c->ex.h_win[WN_XMAX] : 0; }
 int sh_lp_clear_xmax(tw_shard* c) {
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemsetAsync(c->win_buf + WN_XMAX, 0, 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->ex.win_buf + WN_XMAX, 0, 8, c->stream));
     return TW_OK;
 }
 
@@ -1641,8 +1437,8 @@ int sh_lp_clear_xmax(tw_shard* c) {
 static int lp_window_start(tw_shard* c) {
     // (tracing on: tw_lp_batch runs handlers without Lane and would record
     // nothing -- every due record stays on the lane's chain)
-    const bool bat = c->heavy_ok && c->d.lpc_bat && !c->d.trace_cap;
-    if (c->heavy_ok) {
+    const bool bat = c->lpm.heavy_ok && c->d.lpc_bat && !c->d.trace_cap;
+    if (c->lpm.heavy_ok) {
         hipLaunchKernelGGL(tw_lp_due, dim3(TW_DUE_GRID), dim3(256), 0, c->stream, c->dwin());
         HIPCHK(hipGetLastError());
     }
@@ -1663,7 +1459,7 @@ static int lp_window_start(tw_shard* c) {
 
 int sh_lp_loop_begin(tw_shard* c) {
     if (!c) return TW_ERR_INVALID;
-    if (!c->loaded || !c->lp) return TW_ERR_STATE;
+    if (!c->loaded || !c->lpm.lp) return TW_ERR_STATE;
     if (const char* b = getenv("TW_LP_TICK_BUDGET")) {
         const long v = strtol(b, nullptr, 10);
         c->lp_budget = v >= 1 && v <= (1 << 20) ? (uint32_t)v : (1u << 14);
@@ -1673,15 +1469,15 @@ int sh_lp_loop_begin(tw_shard* c) {
         c->lp_grid = v >= 1 && v <= (1 << 20) ? (uint32_t)v : TW_LP_GRID;
     }
     HIPCHK(hipSetDevice(c->device));
-    if (!c->ex_red) c->ex_red = c->red_own;  // world 1 without an explicit setup
+    if (!c->ex.red) c->ex.red = c->ex.red_own;  // world 1 without an explicit setup
     c->d.act_cur = 0;
     c->d.wid = 0;
     hipLaunchKernelGGL(tw_lp_begin, dim3(1), dim3(1), 0, c->stream, c->dwin(), c->d.lookahead);
     HIPCHK(hipGetLastError());
     // the record blocks' counts (tw_lp_ctl clears them every tick; a loop that
     // stopped inside a tick -- a failure on some rank -- may have left some)
-    for (uint32_t g = 0; c->ex_send && g < c->ex_world; ++g)
-        HIPCHK(hipMemsetAsync(c->ex_send + (size_t)g * (c->ex_cap + 1) * 2, 0, sizeof(uint4), c->stream));
+    for (uint32_t g = 0; c->ex.send && g < c->ex.world; ++g)
+        HIPCHK(hipMemsetAsync(c->ex.send + (size_t)g * (c->ex.cap + 1) * 2, 0, sizeof(uint4), c->stream));
     if (c->d.rw) {  // every replica's first window starts at 0; minima empty
         const size_t nrep = (size_t)1 << c->d.rep_lg;
         HIPCHK(hipMemsetAsync(c->d.rw + RW_T * nrep, 0, 8 * nrep, c->stream));
@@ -1690,7 +1486,7 @@ int sh_lp_loop_begin(tw_shard* c) {
     HIPCHK(hipMemsetAsync(c->d.lp_err, 0, 4, c->stream));
     int rc = lp_window_start(c);
     if (rc) return rc;
-    c->loop_ready = true;
+    c->ex.loop_ready = true;
     return TW_OK;
 }
 
@@ -1701,40 +1497,40 @@ static uint32_t lp_grid(uint32_t n) {
 
 int sh_lp_tick(tw_shard* c) {
     if (!c) return TW_ERR_INVALID;
-    if (!c->loaded || !c->lp || !c->loop_ready) return TW_ERR_STATE;
+    if (!c->loaded || !c->lpm.lp || !c->ex.loop_ready) return TW_ERR_STATE;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const Dev d = c->dwin();
     // the window comes from the device (tw_run_kernel reads c.win); launch
     // arguments are captured at enqueue, so d.win is set only around it
-    c->d.win = c->win_buf;
+    c->d.win = c->ex.win_buf;
     launch_run<GeoLP>(c, st, 0, UINT64_MAX, c->lp_budget);
     c->d.win = nullptr;
     HIPCHK(hipGetLastError());
-    if (c->ex_world > 1 && d.carry) {  // the previous tick's carry claims block slots first
-        hipLaunchKernelGGL(tw_lp_pack_carry, dim3(lp_grid(d.carry_cap)), dim3(256), 0, st, d, c->ex_send,
-                           (const uint32_t*)c->ex_starts, c->ex_world, c->ex_cap, c->ex_cap_eff);
+    if (c->ex.world > 1 && d.carry) {  // the previous tick's carry claims block slots first
+        hipLaunchKernelGGL(tw_lp_pack_carry, dim3(lp_grid(d.carry_cap)), dim3(256), 0, st, d, c->ex.send,
+                           (const uint32_t*)c->ex.starts, c->ex.world, c->ex.cap, c->ex.cap_eff);
         HIPCHK(hipGetLastError());
     }
-    hipLaunchKernelGGL(tw_lp_pack, dim3(lp_grid(d.out_cap)), dim3(256), 0, st, d, c->ex_send,
-                       (const uint32_t*)c->ex_starts, c->ex_world, c->ex_cap, c->ex_cap_eff);
+    hipLaunchKernelGGL(tw_lp_pack, dim3(lp_grid(d.out_cap)), dim3(256), 0, st, d, c->ex.send,
+                       (const uint32_t*)c->ex.starts, c->ex.world, c->ex.cap, c->ex.cap_eff);
     HIPCHK(hipGetLastError());
     return TW_OK;
 }
 
 int sh_lp_tick_import(tw_shard* c) {
     if (!c) return TW_ERR_INVALID;
-    if (!c->loaded || !c->lp || !c->loop_ready) return TW_ERR_STATE;
+    if (!c->loaded || !c->lpm.lp || !c->ex.loop_ready) return TW_ERR_STATE;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     // (no exchange buffers -- one rank of a caller-driven loop: tw_lp_ctl
     // fills the words itself)
-    if (c->ex_send) {
-        hipLaunchKernelGGL(tw_lp_import, dim3(lp_grid(c->ex_world * c->ex_cap_eff)), dim3(256), 0, st, c->dwin(),
-                           (const uint4*)c->ex_recv, c->ex_world, c->ex_cap, c->ex_cap_eff);
+    if (c->ex.send) {
+        hipLaunchKernelGGL(tw_lp_import, dim3(lp_grid(c->ex.world * c->ex.cap_eff)), dim3(256), 0, st, c->dwin(),
+                           (const uint4*)c->ex.recv, c->ex.world, c->ex.cap, c->ex.cap_eff);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(tw_lp_fill, dim3(1), dim3(1), 0, st, c->dwin(), c->ex_red, (const uint4*)c->ex_send,
-                           c->ex_world, c->ex_cap);
+        hipLaunchKernelGGL(tw_lp_fill, dim3(1), dim3(1), 0, st, c->dwin(), c->ex.red, (const uint4*)c->ex.send,
+                           c->ex.world, c->ex.cap);
         HIPCHK(hipGetLastError());
     }
     return TW_OK;
@@ -1742,10 +1538,10 @@ int sh_lp_tick_import(tw_shard* c) {
 
 int sh_lp_tick_end(tw_shard* c) {
     if (!c) return TW_ERR_INVALID;
-    if (!c->loaded || !c->lp || !c->loop_ready) return TW_ERR_STATE;
+    if (!c->loaded || !c->lpm.lp || !c->ex.loop_ready) return TW_ERR_STATE;
     HIPCHK(hipSetDevice(c->device));
-    hipLaunchKernelGGL(tw_lp_ctl, dim3(1), dim3(1), 0, c->stream, c->dwin(), c->ex_red, c->ex_send, c->ex_world,
-                       c->ex_cap, c->ex_send ? 1u : 0u);
+    hipLaunchKernelGGL(tw_lp_ctl, dim3(1), dim3(1), 0, c->stream, c->dwin(), c->ex.red, c->ex.send, c->ex.world,
+                       c->ex.cap, c->ex.send ? 1u : 0u);
     HIPCHK(hipGetLastError());
     if (c->d.rw) {
         const uint32_t nrep = 1u << c->d.rep_lg;
@@ -1759,14 +1555,14 @@ int sh_lp_tick_end(tw_shard* c) {
 
 // the window words + lp_err into the pinned host copy (stream-ordered)
 static int lp_progress_copy(tw_shard* c) {
-    int64_t* w = c->h_win;  // pinned: plain DMA copies, no staging blit
-    HIPCHK(hipMemcpyAsync(w, c->win_buf, 8 * WN_COUNT, hipMemcpyDeviceToHost, c->stream));
+    int64_t* w = c->ex.h_win;  // pinned: plain DMA copies, no staging blit
+    HIPCHK(hipMemcpyAsync(w, c->ex.win_buf, 8 * WN_COUNT, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(w + WN_COUNT, c->d.lp_err, 4, hipMemcpyDeviceToHost, c->stream));
     return TW_OK;
 }
 static int lp_progress_read(tw_shard* c, tw_lp_state* out) {
     HIPCHK(hipStreamSynchronize(c->stream));
-    const int64_t* w = c->h_win;
+    const int64_t* w = c->ex.h_win;
     const uint32_t err = (uint32_t)w[WN_COUNT];
     out->windows = (uint64_t)w[WN_WINDOWS];
     out->ticks = (uint64_t)w[WN_TICKS];
@@ -1776,17 +1572,17 @@ static int lp_progress_read(tw_shard* c, tw_lp_state* out) {
     return TW_OK;
 }
 static int lp_host_alloc(tw_shard* c) {
-    if (!c->h_win) HIPCHK(hipHostMalloc((void**)&c->h_win, 8 * (WN_COUNT + 1)));
+    if (!c->ex.h_win) HIPCHK(hipHostMalloc((void**)&c->ex.h_win, 8 * (WN_COUNT + 1)));
     return TW_OK;
 }
 
 int sh_lp_progress(tw_shard* c, tw_lp_state* out) {
     if (!c || !out) return TW_ERR_INVALID;
-    if (!c->loaded || !c->lp || !c->loop_ready) return TW_ERR_STATE;
+    if (!c->loaded || !c->lpm.lp || !c->ex.loop_ready) return TW_ERR_STATE;
     HIPCHK(hipSetDevice(c->device));
     int rc = lp_host_alloc(c);
     if (rc) return rc;
-    c->h_win[WN_COUNT] = 0;  // lp_err fills its low 4 bytes
+    c->ex.h_win[WN_COUNT] = 0;  // lp_err fills its low 4 bytes
     rc = lp_progress_copy(c);
     return rc ? rc : lp_progress_read(c, out);
 }
@@ -1806,19 +1602,19 @@ static std::vector<unsigned char> tick_key(const tw_shard* c) {
     std::memset(&k, 0, sizeof(k));
     std::memcpy(&k.d, &c->d, sizeof(Dev));
     k.st = c->stream;
-    k.win = c->win_buf;
-    k.h_win = c->h_win;
-    k.red = c->ex_red;
-    k.send = c->ex_send;
-    k.recv = c->ex_recv;
-    k.starts = c->ex_starts;
+    k.win = c->ex.win_buf;
+    k.h_win = c->ex.h_win;
+    k.red = c->ex.red;
+    k.send = c->ex.send;
+    k.recv = c->ex.recv;
+    k.starts = c->ex.starts;
     k.budget = c->lp_budget;
     k.grid = c->lp_grid;
-    k.world = c->ex_world;
-    k.cap = c->ex_cap;
-    k.cap_eff = c->ex_cap_eff;
+    k.world = c->ex.world;
+    k.cap = c->ex.cap;
+    k.cap_eff = c->ex.cap_eff;
     k.lds = c->lds_bytes;
-    k.heavy = c->heavy_ok;
+    k.heavy = c->lpm.heavy_ok;
     std::vector<unsigned char> v(sizeof(K));
     std::memcpy(v.data(), &k, sizeof(K));
     return v;
@@ -1828,10 +1624,8 @@ static std::vector<unsigned char> tick_key(const tw_shard* c) {
 // same graph serves every batch; ticks after the loop is done return at once)
 static int tick_graph_ready(tw_shard* c) {
     std::vector<unsigned char> key = tick_key(c);
-    if (c->tick_graph && key == c->tick_gkey) return TW_OK;
-    if (c->tick_graph) (void)hipGraphExecDestroy(c->tick_graph);
-    c->tick_graph = nullptr;
-    c->tick_gkey.clear();
+    if (c->tg.exec && key == c->tg.key) return TW_OK;
+    c->tg.unload();
     HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
     int rc = TW_OK;
     for (int i = 0; i < TW_GRAPH_TICKS && !rc; ++i) {
@@ -1847,20 +1641,20 @@ static int tick_graph_ready(tw_shard* c) {
         (void)hipGetLastError();
         return rc ? rc : TW_ERR_HIP;
     }
-    const hipError_t ei = hipGraphInstantiate(&c->tick_graph, g, nullptr, nullptr, 0);
+    const hipError_t ei = hipGraphInstantiate(&c->tg.exec, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
     if (ei != hipSuccess) {
-        c->tick_graph = nullptr;
+        c->tg.exec = nullptr;
         return TW_ERR_HIP;
     }
-    c->tick_gkey = std::move(key);
+    c->tg.key = std::move(key);
     return TW_OK;
 }
 
 int sh_lp_run_windows(tw_shard* c, uint64_t max_ticks, tw_lp_state* out) {
     if (!c || !out) return TW_ERR_INVALID;
-    if (!c->loaded || !c->lp || !c->loop_ready) return TW_ERR_STATE;
-    if (c->ex_world != 1) return TW_ERR_STATE;
+    if (!c->loaded || !c->lpm.lp || !c->ex.loop_ready) return TW_ERR_STATE;
+    if (c->ex.world != 1) return TW_ERR_STATE;
     HIPCHK(hipSetDevice(c->device));
     int rc = lp_host_alloc(c);
     if (rc) return rc;
@@ -1869,11 +1663,11 @@ int sh_lp_run_windows(tw_shard* c, uint64_t max_ticks, tw_lp_state* out) {
     for (uint64_t done_ticks = 0; done_ticks < max_ticks;) {
         const uint64_t batch =
             max_ticks - done_ticks < TW_GRAPH_TICKS ? max_ticks - done_ticks : (uint64_t)TW_GRAPH_TICKS;
-        c->h_win[WN_COUNT] = 0;  // lp_err fills its low 4 bytes
+        c->ex.h_win[WN_COUNT] = 0;  // lp_err fills its low 4 bytes
         if (graph && batch == TW_GRAPH_TICKS) {
             rc = tick_graph_ready(c);
             if (rc) return rc;
-            HIPCHK(hipGraphLaunch(c->tick_graph, c->stream));
+            HIPCHK(hipGraphLaunch(c->tg.exec, c->stream));
         } else {
             for (uint64_t i = 0; i < batch; ++i) {
                 rc = sh_lp_tick(c);
@@ -1900,15 +1694,15 @@ static int lpb_run(tw_shard* c, tw_stats* out) {
     // after tw_reset (no reduction pass needed)
     std::vector<tw_replica_result> before;
     if (out) {
-        before.resize(c->n_rep);
-        if (c->lpb_fresh) {
+        before.resize(c->lpm.n_rep);
+        if (c->lpm.fresh) {
             std::memset(before.data(), 0, sizeof(tw_replica_result) * before.size());
         } else {
             int rc = sh_read_results(c, before.data(), before.size());
             if (rc) return rc;
         }
     }
-    c->lpb_fresh = false;
+    c->lpm.fresh = false;
     int rc = sh_lp_loop_begin(c);
     if (rc) return rc;
     c->times.start();
@@ -1919,15 +1713,15 @@ static int lpb_run(tw_shard* c, tw_stats* out) {
     HIPCHK(hipStreamSynchronize(c->stream));
     rc = c->times.read();
     if (rc) return rc;
-    c->lpb_windows = ls.windows;
-    c->lpb_ticks = ls.ticks;
+    c->lpm.windows = ls.windows;
+    c->lpm.ticks = ls.ticks;
     if (rcw) return rcw;
     if (out) {
         std::memset(out, 0, sizeof(*out));
-        std::vector<tw_replica_result> rr(c->n_rep);
+        std::vector<tw_replica_result> rr(c->lpm.n_rep);
         rc = sh_read_results(c, rr.data(), rr.size());
         if (rc) return rc;
-        for (uint32_t i = 0; i < c->n_rep; ++i) {
+        for (uint32_t i = 0; i < c->lpm.n_rep; ++i) {
             out->events += rr[i].events - before[i].events;
             out->delivered += rr[i].delivered - before[i].delivered;
             out->dropped += rr[i].dropped - before[i].dropped;
@@ -1946,15 +1740,15 @@ static int lpb_run(tw_shard* c, tw_stats* out) {
 
 int sh_lpb_windows(tw_shard* c, uint64_t* windows, uint64_t* ticks) {
     if (!c) return TW_ERR_INVALID;
-    if (!c->loaded || !c->lpb) return TW_ERR_STATE;
-    if (windows) *windows = c->lpb_windows;
-    if (ticks) *ticks = c->lpb_ticks;
+    if (!c->loaded || !c->lpm.lpb) return TW_ERR_STATE;
+    if (windows) *windows = c->lpm.windows;
+    if (ticks) *ticks = c->lpm.ticks;
     return TW_OK;
 }
 
 int sh_lpb_batch(tw_shard* c, uint64_t* batched, uint64_t* due) {
     if (!c) return TW_ERR_INVALID;
-    if (!c->loaded || !c->lpb) return TW_ERR_STATE;
+    if (!c->loaded || !c->lpm.lpb) return TW_ERR_STATE;
     unsigned long long h[2] = {0, 0};
     if (c->d.bat_ctr) {
         HIPCHK(hipSetDevice(c->device));
@@ -1983,9 +1777,9 @@ int sh_prof_read(tw_shard* c, unsigned long long* out, size_t cap, int reset) {
 #endif
 }
 
-uint32_t sh_replicas(tw_shard* c) { return c->lpb ? c->n_rep : c->d.R; }
-uint32_t sh_nodes(tw_shard* c) { return c->lpb ? c->d.Ntot : c->d.N; }
-bool sh_is_lp(tw_shard* c) { return c->lp; }
+uint32_t sh_replicas(tw_shard* c) { return c->lpm.lpb ? c->lpm.n_rep : c->d.R; }
+uint32_t sh_nodes(tw_shard* c) { return c->lpm.lpb ? c->d.Ntot : c->d.N; }
+bool sh_is_lp(tw_shard* c) { return c->lpm.lp; }
 int sh_device(tw_shard* c) { return c->device; }
 
 int sh_set_trace(tw_shard* c, uint32_t cap) {
@@ -1994,28 +1788,19 @@ int sh_set_trace(tw_shard* c, uint32_t cap) {
     // node-partitioned (tw_lp_load): LP lanes are nodes -- no replica execution
     // order to record, and one counter for all lanes.  Batched LP records per
     // replica, in claim order (Lane::trace_rec)
-    if (c->lp && !c->lpb) return TW_ERR_INVALID;
+    if (c->lpm.lp && !c->lpm.lpb) return TW_ERR_INVALID;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->px.touch();
-    if (c->d.trace) {
-        HIPCHK(hipFree(c->d.trace));
-        c->d.trace = nullptr;
-    }
-    if (c->d.trace_n) {
-        HIPCHK(hipFree(c->d.trace_n));
-        c->d.trace_n = nullptr;
-    }
-    c->d.trace_cap = 0;
+    trace_release(c->d);
     if (cap) {
         // (batched LP: d.R counts lanes)
-        const size_t nrep = c->lpb ? c->n_rep : c->d.R;
+        const size_t nrep = c->lpm.lpb ? c->lpm.n_rep : c->d.R;
         HIPCHK(hipMalloc(&c->d.trace, (size_t)cap * nrep * 32));
-        if (c->lpb) {
+        if (c->lpm.lpb) {
             if (hipMalloc(&c->d.trace_n, 8 * nrep) != hipSuccess) {
                 (void)hipGetLastError();
-                (void)hipFree(c->d.trace);
-                c->d.trace = nullptr;
+                trace_release(c->d);
                 return TW_ERR_OOM;
             }
             HIPCHK(hipMemsetAsync(c->d.trace_n, 0, 8 * nrep, c->stream));
@@ -2030,12 +1815,12 @@ int sh_read_trace(tw_shard* c, uint32_t replica, tw_trace_rec* out, size_t cap, 
     if (!c || (cap && !out)) return TW_ERR_INVALID;
     if (!c->loaded) return TW_ERR_STATE;
     const Dev& d = c->d;
-    if (c->lp && !c->lpb) return TW_ERR_INVALID;
-    const size_t nrep = c->lpb ? c->n_rep : d.R;  // the records' replica stride (batched LP: d.R counts lanes)
+    if (c->lpm.lp && !c->lpm.lpb) return TW_ERR_INVALID;
+    const size_t nrep = c->lpm.lpb ? c->lpm.n_rep : d.R;  // the records' replica stride (batched LP: d.R counts lanes)
     if (replica >= nrep) return TW_ERR_INVALID;
     HIPCHK(hipSetDevice(c->device));
     uint64_t n = 0;
-    if (!c->lpb)
+    if (!c->lpm.lpb)
         HIPCHK(hipMemcpyAsync(&n, d.scal + (size_t)SC_TRACE_N * d.R + replica, 8, hipMemcpyDeviceToHost, c->stream));
     else if (d.trace_n)
         HIPCHK(hipMemcpyAsync(&n, d.trace_n + replica, 8, hipMemcpyDeviceToHost, c->stream));
@@ -2049,7 +1834,7 @@ int sh_read_trace(tw_shard* c, uint32_t replica, tw_trace_rec* out, size_t cap, 
         HIPCHK(hipMemcpy2DAsync(buf.data(), 32, d.trace + (size_t)replica * 2, nrep * 32, 32, k,
                                 hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->lpb) {
+        if (c->lpm.lpb) {
             // claim order says nothing: the canonical order (t, node, tag, val)
             struct Q2 { uint4 a, b; };
             Q2* q = reinterpret_cast<Q2*>(buf.data());
@@ -2076,7 +1861,7 @@ int sh_measure_state(tw_shard* c) {
     // as sh_set_trace: node-partitioned contexts keep no TRACE records.  A
     // batched LP context with tracing off keeps answering TW_ERR_INVALID too
     // (what it answered before it could trace), not TW_ERR_STATE
-    if (c->lp && (!c->lpb || !c->d.trace || !c->d.trace_cap || !c->d.trace_n)) return TW_ERR_INVALID;
+    if (c->lpm.lp && (!c->lpm.lpb || !c->d.trace || !c->d.trace_cap || !c->d.trace_n)) return TW_ERR_INVALID;
     if (!c->d.trace || !c->d.trace_cap) return TW_ERR_STATE;
     return TW_OK;
 }
@@ -2086,8 +1871,8 @@ int sh_measure(tw_shard* c, const tw_measure_spec* spec, const MeasureCfg& cfg, 
     int rc = sh_measure_state(c);
     if (rc) return rc;
     const Dev& d = c->d;
-    if (c->lpb)  // (one count per replica in trace_n; d.R counts lanes)
-        return measure_run(c->device, c->stream, d.trace, d.trace_n, c->n_rep, d.trace_cap, spec, cfg, total, hist, per,
+    if (c->lpm.lpb)  // (one count per replica in trace_n; d.R counts lanes)
+        return measure_run(c->device, c->stream, d.trace, d.trace_n, c->lpm.n_rep, d.trace_cap, spec, cfg, total, hist, per,
                            kernel_ms, phase_ms);
     return measure_run(c->device, c->stream, d.trace, d.scal + (size_t)SC_TRACE_N * d.R, d.R, d.trace_cap, spec, cfg,
                        total, hist, per, kernel_ms, phase_ms);

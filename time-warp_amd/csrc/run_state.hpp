@@ -1,7 +1,10 @@
-// run_state.hpp -- host-only state of tw_run's stages (engine.hip): the timed
-// launches, the killThread sweeps and the send-free prefix.  Each feature's
-// state is one member of tw_shard and knows how to reset itself: a field added
-// here goes back to its default at a tw_load unless `unload` carries it over.
+// run_state.hpp -- host-only state of a context (engine.hip's tw_shard): the
+// timed launches, the killThread sweeps, the send-free prefix, the run's
+// statistics buffers, the LP modes, the device loop's exchange and its tick
+// graph.  Each feature's state is one member of tw_shard and knows how to reset
+// itself: a field added here goes back to its default at a tw_load unless
+// `unload` carries it over, and a feature that owns device or pinned memory
+// frees it here and nowhere else (DESIGN §3p has the table).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -90,6 +93,11 @@ struct Sweep {
         for (int k = 0; k < 3; ++k) z.last[k] = last[k];
         *this = z;
     }
+    void destroy() {
+        unload();
+        if (h) (void)hipHostFree(h);
+        h = nullptr;
+    }
 };
 
 // the send-free prefix (prefix.hip): the image's bound T0
@@ -157,5 +165,123 @@ struct Prefix {
         Prefix z;
         z.last = last; z.ms = ms; z.audit = audit;
         *this = z;
+    }
+};
+
+// tw_run's statistics reduced on the device (tw_stats_kernel): the events
+// column at the run's start, the 8 result words (both the feature's own,
+// allocated by the first run that asks for statistics) and their pinned copy
+struct StatBuf {
+    uint64_t* ev0 = nullptr;
+    unsigned long long* out = nullptr;
+    unsigned long long* h = nullptr;    // pinned; outlives loads
+
+    void unload() {
+        if (ev0) (void)hipFree(ev0);
+        if (out) (void)hipFree(out);
+        ev0 = nullptr;
+        out = nullptr;
+    }
+    void destroy() {
+        unload();
+        if (h) (void)hipHostFree(h);
+        h = nullptr;
+    }
+};
+
+// The TRACE buffer (tw_set_trace).  Dev holds its pointers, for the kernels;
+// the buffer is its own (not among the context's allocations) and this is its
+// one release: a new tw_set_trace, and every unload.
+inline void trace_release(tw::Dev& d) {
+    if (d.trace) (void)hipFree(d.trace);
+    if (d.trace_n) (void)hipFree(d.trace_n);
+    d.trace = nullptr;
+    d.trace_n = nullptr;
+    d.trace_cap = 0;
+}
+
+// The LP modes (tw_lp_load, tw_lpb_load): what the load decided and the
+// host-driven window's buffers (among the context's allocations)
+struct LpMode {
+    bool lp = false;
+    bool lpb = false;               // batched LP (tw_lpb_load): R = nodes x replicas
+    uint32_t n_rep = 1;             // replicas batched per node
+    bool heavy_ok = false;          // some node's inbox can exceed TW_LIGHT (tw_lp_due runs)
+    bool has_ph1 = false;           // two-phase windows (Dev::phase)
+    bool fresh = false;             // tw_reset since the last batched-LP tw_run: every counter is 0
+    uint64_t windows = 0, ticks = 0;  // of the last batched-LP tw_run; outlive loads, like the sweeps' counts
+    uint4* foreign = nullptr;       // [out_cap][2]
+    uint32_t* n_foreign = nullptr;
+    uint4* staging = nullptr;       // inject staging [out_cap][2]
+
+    void unload() {
+        LpMode z;
+        z.windows = windows; z.ticks = ticks;
+        *this = z;
+    }
+};
+
+// device-driven windows (tw_lp_exchange_setup / sh_lp_exchange_own): blocks of
+// `cap` records (the stride) of which the first cap_eff go over the wire this
+// tick (<= cap; the library loop adapts it).  The exchange owns `starts`, `own`
+// and `carry`; `send`, `recv` and `red` point into `own` or are the caller's;
+// win_buf and red_own are among the context's allocations.
+struct Exchange {
+    uint32_t world = 1, rank = 0, cap = 0, cap_eff = 0;
+    uint32_t* starts = nullptr;       // device, world + 1
+    uint4* send = nullptr;            // caller's device buffers (or own's)
+    uint4* recv = nullptr;
+    int64_t* red = nullptr;           // caller's (or red_own, or own's)
+    int64_t* red_own = nullptr;
+    void* own = nullptr;              // library-owned send | recv | red (sh_lp_exchange_own)
+    void* carry = nullptr;            // Dev::carry + carry_n
+    int64_t* win_buf = nullptr;       // the device loop's WN_* words
+    int64_t* h_win = nullptr;         // pinned host copy of them + lp_err (tw_lp_progress); outlives loads
+    bool loop_ready = false;
+
+    // Dev's view of the carry block: counts in its first 256 bytes, then the records
+    void set_carry(tw::Dev& d, uint32_t records) const {
+        d.carry_n = carry ? (uint32_t*)carry : nullptr;
+        d.carry = carry ? (uint4*)((char*)carry + 256) : nullptr;
+        d.carry_cap = carry ? records : 0u;
+    }
+    // forget the ranks and free the blocks the exchange owns (a new setup, unload)
+    void drop(tw::Dev& d) {
+        if (starts) (void)hipFree(starts);
+        if (own) (void)hipFree(own);
+        if (carry) (void)hipFree(carry);
+        starts = nullptr;
+        own = carry = nullptr;
+        set_carry(d, 0);
+        send = recv = nullptr;
+        red = nullptr;
+        world = 1;
+        rank = cap = cap_eff = 0;
+    }
+    void unload(tw::Dev& d) {
+        drop(d);
+        Exchange z;
+        z.h_win = h_win;
+        *this = z;
+    }
+    void destroy(tw::Dev& d) {
+        unload(d);
+        if (h_win) (void)hipHostFree(h_win);
+        h_win = nullptr;
+    }
+};
+
+// sh_lp_run_windows: TW_GRAPH_TICKS ticks + the progress copy captured as one
+// hipGraph (a tick is 4-8 short kernels: launched one by one, the host's
+// enqueue rate left the device idle between them), re-captured when the
+// launch arguments it holds change (key)
+struct TickGraph {
+    hipGraphExec_t exec = nullptr;
+    std::vector<unsigned char> key;
+
+    void unload() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        exec = nullptr;
+        key.clear();
     }
 };
