@@ -373,13 +373,28 @@ typedef struct tw_trace_rec {
  * nodes run as separate lanes, each record claims the replica's next index
  * with one atomic (8 more bytes of HBM per replica), and the records are kept
  * in claim order, which is no execution order (see tw_read_trace).  While
- * tracing is on, such a context runs every due record on its node's chain: the
- * data-parallel batch of tw_lpb_batch records nothing and stays off, so a
- * traced run of a hotspot is slower than an untraced one.
+ * tracing is on, such a context by default runs every due record on its node's
+ * chain: the data-parallel batch of tw_lpb_batch stays off, so a traced run of
+ * a hotspot is slower than an untraced one; tw_set_trace_batch keeps the batch
+ * on and has it record.
  * TW_ERR_INVALID for a node-partitioned context (tw_lp_load): its lanes are
  * the nodes of one replica spread over contexts -- there is no replica
  * execution order to record, and no one counter all of them could claim from. */
 int tw_set_trace(tw_ctx* ctx, uint32_t cap);
+
+/* A tw_lpb_load context with tracing on: on != 0 keeps the data-parallel batch
+ * of tw_lpb_batch running, in a variant that records the TRACEs of the due
+ * records it handles -- one claim on the replica's counter per node and window
+ * instead of one per record.  The kept records of a replica below the trace
+ * cap are the same multiset either way, tw_read_trace's canonical order and
+ * tw_measure do not tell the two apart, and results and hashes do not change.
+ * A due record whose handler traces more than 63 times stays on the chain.
+ * Off (0) after every tw_lpb_load: with few records per node and window the
+ * chain is the faster of the two.  Takes effect from the next tw_reset, for
+ * every shard of the context; with tracing off, or with TW_LP_BATCH=0 at the
+ * load, it changes nothing.  TW_ERR_STATE before a load; TW_ERR_INVALID for a
+ * context not loaded with tw_lpb_load (tw_load, tw_lp_load). */
+int tw_set_trace_batch(tw_ctx* ctx, int on);
 
 /* A replica's trace records: copies min(cap, emitted, trace cap) records and
  * stores the number emitted (possibly more than were kept) in *n_emitted.
@@ -708,8 +723,9 @@ int tw_lpb_windows(tw_ctx* ctx, uint64_t* windows, uint64_t* ticks);
  * one send followed by END; bench/Network's Ping handler) and no other event of
  * the node falls between their events.  Results are those of the sequential
  * loop either way; TW_LP_BATCH=0 at tw_lpb_load turns the batch off, and so
- * does tw_set_trace with a cap > 0 (the batch keeps no TRACE records: batched
- * stays 0 and the due records run on their nodes' chains). */
+ * does tw_set_trace with a cap > 0 unless tw_set_trace_batch is on (the plain
+ * batch keeps no TRACE records: batched stays 0 and the due records run on
+ * their nodes' chains). */
 int tw_lpb_batch(tw_ctx* ctx, uint64_t* batched, uint64_t* due_records);
 
 /* ---- device-driven windows (no host round trip per window)

@@ -615,6 +615,15 @@ int tw_set_trace(tw_ctx* c, uint32_t cap) {
     return TW_OK;
 }
 
+int tw_set_trace_batch(tw_ctx* c, int on) {
+    if (!c) return TW_ERR_INVALID;
+    for (tw_shard* s : c->sh) {  // (checked before any shard changes: a context's shards are of one kind)
+        int rc = sh_set_trace_batch(s, on);
+        if (rc) return rc;
+    }
+    return TW_OK;
+}
+
 int tw_read_trace(tw_ctx* c, uint32_t replica, tw_trace_rec* out, size_t cap, uint64_t* n_emitted) {
     if (!c) return TW_ERR_INVALID;
     for (size_t i = c->sh.size(); i-- > 0;) {

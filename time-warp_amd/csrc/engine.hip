@@ -645,6 +645,7 @@ int sh_reset(tw_shard* c) {
         c->d.wid = 0;
         HIPCHK(hipMemsetAsync(d.act_n, 0, 8 * TW_LP_NB, st));
         c->lpm.fresh = c->lpm.lpb;
+        c->lpm.trace_bat_run = c->lpm.trace_bat;  // (tw_set_trace_batch: from this reset on)
     }
     if (d.pq_hdr) {
         // empty MinQueues: no element, no node used, every rank a Skip
@@ -1436,8 +1437,10 @@ int sh_lp_clear_xmax(tw_shard* c) {
 // per CU wide)
 static int lp_window_start(tw_shard* c) {
     // (tracing on: tw_lp_batch runs handlers without Lane and would record
-    // nothing -- every due record stays on the lane's chain)
-    const bool bat = c->lpm.heavy_ok && c->d.lpc_bat && !c->d.trace_cap;
+    // nothing -- every due record stays on the lane's chain, unless
+    // tw_set_trace_batch asked for tw_lp_batch<true>, which records)
+    const bool tr = c->d.trace_cap != 0;
+    const bool bat = c->lpm.heavy_ok && c->d.lpc_bat && (!tr || c->lpm.trace_bat_run);
     if (c->lpm.heavy_ok) {
         hipLaunchKernelGGL(tw_lp_due, dim3(TW_DUE_GRID), dim3(256), 0, c->stream, c->dwin());
         HIPCHK(hipGetLastError());
@@ -1451,7 +1454,8 @@ static int lp_window_start(tw_shard* c) {
     }
     HIPCHK(hipGetLastError());
     if (bat) {
-        hipLaunchKernelGGL(tw_lp_batch, dim3(TW_DUE_GRID), dim3(TW_BAT_T), 0, c->stream, c->dwin());
+        hipLaunchKernelGGL(tr ? tw_lp_batch<true> : tw_lp_batch<false>, dim3(TW_DUE_GRID), dim3(TW_BAT_T), 0,
+                           c->stream, c->dwin());
         HIPCHK(hipGetLastError());
     }
     return TW_OK;
@@ -1597,7 +1601,7 @@ static std::vector<unsigned char> tick_key(const tw_shard* c) {
         uint4 *send, *recv;
         uint32_t *starts, budget, grid, world, cap, cap_eff;
         size_t lds;
-        bool heavy;
+        bool heavy, trace_bat;
     } k;
     std::memset(&k, 0, sizeof(k));
     std::memcpy(&k.d, &c->d, sizeof(Dev));
@@ -1615,6 +1619,7 @@ static std::vector<unsigned char> tick_key(const tw_shard* c) {
     k.cap_eff = c->ex.cap_eff;
     k.lds = c->lds_bytes;
     k.heavy = c->lpm.heavy_ok;
+    k.trace_bat = c->lpm.trace_bat_run;
     std::vector<unsigned char> v(sizeof(K));
     std::memcpy(v.data(), &k, sizeof(K));
     return v;
@@ -1808,6 +1813,14 @@ int sh_set_trace(tw_shard* c, uint32_t cap) {
         }
         c->d.trace_cap = cap;
     }
+    return TW_OK;
+}
+
+int sh_set_trace_batch(tw_shard* c, int on) {
+    if (!c) return TW_ERR_INVALID;
+    if (!c->loaded) return TW_ERR_STATE;
+    if (!c->lpm.lpb) return TW_ERR_INVALID;  // (tw_lp_batch serves batched LP contexts only)
+    c->lpm.trace_bat = on != 0;
     return TW_OK;
 }
 

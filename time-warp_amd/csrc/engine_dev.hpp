@@ -3784,8 +3784,28 @@ struct BProg {
     const uint32_t LAS* LPC;
     const uint8_t LAS* BAT;
 };
-__device__ DueX due_exec(const Dev& c, const BProg& bp, uint32_t r, uint32_t set, uint4 a, uint4 b) {
+// TR (tw_lp_batch<true>; tw_set_trace_batch): the handler's TRACE records.
+// *ntr counts them, one per U_TR and one more per U_TR2, in the order the
+// chain executes them; with tr_at != TW_TR_COUNT the k-th is also written, as
+// Lane::trace_rec writes it, at the replica's index tr_at + k (while below the
+// cap: the claimed count goes on past it).  The caller hands out indexes only
+// for records it keeps (ok = 1), so a path that leaves the admitted code
+// records nothing the chain would not record itself.
+#define TW_TR_COUNT (~0ull)
+__device__ __forceinline__ void due_trace(const Dev& c, uint32_t rho, unsigned long long n, int64_t t, uint32_t node,
+                                          int32_t tag, int64_t val) {
+    if (n < c.trace_cap) {
+        uint4 GAS* q = gp(c.trace) + ((((size_t)n << c.rep_lg) + rho) * 2);
+        q[0] = make_uint4((uint32_t)t, (uint32_t)((uint64_t)t >> 32), node, (uint32_t)tag);
+        q[1] = make_uint4((uint32_t)val, (uint32_t)((uint64_t)val >> 32), 0u, 0u);
+    }
+}
+template <bool TR>
+__device__ DueX due_exec(const Dev& c, const BProg& bp, uint32_t r, uint32_t set, uint4 a, uint4 b,
+                         unsigned long long tr_at = TW_TR_COUNT, uint32_t* ntr = nullptr) {
     DueX o{};
+    [[maybe_unused]] uint32_t nt = 0;
+    if constexpr (TR) *ntr = 0;
     o.hs_lane = 0xFFFFFFFFu;
     const int64_t t = ent_t(a);
     const int64_t payload = (int64_t)(((uint64_t)a.w << 32) | a.z);
@@ -3909,6 +3929,17 @@ __device__ DueX due_exec(const Dev& c, const BProg& bp, uint32_t r, uint32_t set
         }
         if (f & U_TR) o.h += term(t, TW_KIND_TRACE | ((uint32_t)imm & 0xFFFFu), ra);
         if (f & U_TR2) o.h += term(t, TW_KIND_TRACE | (b16 & 0x1FFFu), rr[(b16 >> 13) & 3u]);
+        if constexpr (TR) {
+            if (f & U_TR) {
+                if (tr_at != TW_TR_COUNT) due_trace(c, rho, tr_at + nt, t, node, imm, ra);
+                *ntr = ++nt;
+            }
+            if (f & U_TR2) {
+                if (tr_at != TW_TR_COUNT)
+                    due_trace(c, rho, tr_at + nt, t, node, (int32_t)(b16 & 0x1FFFu), rr[(b16 >> 13) & 3u]);
+                *ntr = ++nt;
+            }
+        }
         if (f & U_P2) tgt = pc + 2;
         if (jm != JM_NONE) {
             const int64_t bb = (int64_t)(int16_t)b16;
@@ -4136,6 +4167,19 @@ static_assert(TW_BAT_T % 64 == 0 && TW_BAT_T <= 256 && TW_BATCH_CAP % TW_BAT_T =
 // spill, far-heap top and spawn count by threads 64..65+TW_NEAR_LP (wave 1):
 // a narrower workgroup would leave sS / sNear / bFarT / bSpn unwritten
 static_assert(SC_COUNT <= TW_BAT_T && 66u + TW_NEAR_LP <= TW_BAT_T, "tw_lp_batch's loader threads exist");
+//
+// TR (tw_lp_batch<true>, launched instead while tw_set_trace and
+// tw_set_trace_batch are both on): the prefix's TRACE records.  The
+// dry run leaves each record's count in the six free bits of its dix byte (no
+// LDS to spare: a fifth workgroup's worth is 288 B away), and a record that
+// traces more than 63 times stays on the chain.  Once the prefix is known,
+// thread tid takes the records [tid q, tid q + q) of it, q = ceil(K / TW_BAT_T):
+// contiguous, so a thread's exclusive scan value is the index of its first
+// record's first TRACE and no per-record scan needs storing.  One returning
+// atomic on trace_n[replica] claims the lane's records of the window (the
+// chain: one per record); the effects pass re-executes every record that
+// traces and writes its records from the claimed base on.
+template <bool TR>
 __global__ void __launch_bounds__(TW_BAT_T) tw_lp_batch(Dev c) {
     const int64_t GAS* w = gp(c.win);
     const int64_t fl = w[WN_FLAGS];
@@ -4152,7 +4196,7 @@ __global__ void __launch_bounds__(TW_BAT_T) tw_lp_batch(Dev c) {
     __shared__ uint32_t sL[TW_BATCH_LPC];
     __shared__ uint8_t sB[TW_BATCH_LPC];
     __shared__ uint4 ea[TW_BATCH_CAP + 1], eb[TW_BATCH_CAP];
-    __shared__ uint8_t dix[TW_BATCH_CAP];      // per record: batchable | yielded << 1
+    __shared__ uint8_t dix[TW_BATCH_CAP];      // per record: batchable | yielded << 1 | TR: its TRACE count << 2
     __shared__ int64_t wmx[4], sNear[8];
     __shared__ uint64_t sS[SC_COUNT];          // the lane's scalar block
     __shared__ uint32_t bSet, bK0, bK, bDirect, bNd, bNx;
@@ -4208,7 +4252,7 @@ __global__ void __launch_bounds__(TW_BAT_T) tw_lp_batch(Dev c) {
             // in-place fork_); a batched prefix never overlaps two records, so
             // one free slot is what the chain needs -- a full lane stays on the
             // chain, which fails it with TW_REP_ERR_SLOTS at the first due pop
-            const bool el = nd0 && c.trace_cap == 0 && c.tie_mode == TW_TIE_FIFO &&
+            const bool el = nd0 && (TR ? c.trace_n != nullptr : c.trace_cap == 0) && c.tie_mode == TW_TIE_FIFO &&
                             (sS[SC_FREE_N] > 0 || sS[SC_BUMP] < (uint64_t)c.S) &&
                             sS[SC_STATUS] == TW_REP_RUNNING && sS[SC_PENDING_MAIN] == 0 &&
                             !bSpn && sS[SC_SEQ] + 3ull * nd0 < 0xFFFFFFFFull &&
@@ -4238,12 +4282,18 @@ __global__ void __launch_bounds__(TW_BAT_T) tw_lp_batch(Dev c) {
         // dry run: batchable | yielded << 1 per record (due order); each thread
         // keeps its first record's outcome for the effects
         DueX x0{};
+        [[maybe_unused]] uint32_t ntr0 = 0;  // (TR: x0's TRACE count)
         for (uint32_t i = tid; i < nd; i += TW_BAT_T) {
-            const DueX x = due_exec(c, bp, r, bSet, ea[i], eb[i]);
-            const bool ok = x.ok && x.last < bTo;
-            dix[i] = (uint8_t)((ok ? 1u : 0u) | (x.yld ? 2u : 0u));
+            // (no pointer without TR: handing &ntr to the untraced instantiation
+            // alone reorders its registers against the kernel as it was)
+            [[maybe_unused]] uint32_t ntr = 0;
+            const DueX x = due_exec<TR>(c, bp, r, bSet, ea[i], eb[i], TW_TR_COUNT, TR ? &ntr : nullptr);
+            const bool ok = x.ok && x.last < bTo && (!TR || ntr < 64u);  // (TR: the count fits dix's six bits)
+            dix[i] = (uint8_t)((ok ? 1u : 0u) | (x.yld ? 2u : 0u) | (TR && ok ? ntr << 2 : 0u));
             if (!ok) atomicMin(&bK0, i);
             if (i == tid) x0 = x;
+            if constexpr (TR)
+                if (i == tid) ntr0 = ntr;
         }
         __syncthreads();
         BT(bt2);
@@ -4286,17 +4336,56 @@ __global__ void __launch_bounds__(TW_BAT_T) tw_lp_batch(Dev c) {
         }
         __syncthreads();
         BT(bt3);
+        const uint32_t K = bK;
+        // TR: the thread's records of the prefix are [i0, i1)
+        [[maybe_unused]] uint32_t i0 = 0, i1 = 0;
+        [[maybe_unused]] unsigned long long tr_at = 0;  // TR: the replica's index of the thread's next TRACE record
+        if constexpr (TR) {
+            if (K) {  // (uniform)
+                __shared__ unsigned long long bTrAt;
+                const uint32_t q = (K + TW_BAT_T - 1u) / TW_BAT_T;
+                i0 = tid * q < K ? tid * q : K;
+                i1 = i0 + q < K ? i0 + q : K;
+                uint32_t cnt = 0;
+                for (uint32_t i = i0; i < i1; ++i) cnt += dix[i] >> 2;
+                uint32_t inc = cnt;
+#pragma unroll
+                for (uint32_t d = 1; d < 64; d <<= 1) {
+                    const uint32_t o = __shfl_up(inc, d, 64);
+                    if (lane >= d) inc += o;
+                }
+                if (lane == 63) wmx[wv] = (int64_t)inc;  // (the prefix scan's readers are past the barrier above)
+                __syncthreads();
+                uint32_t before = inc - cnt, total = 0;
+                for (uint32_t k = 0; k < TW_BAT_T / 64u; ++k) {
+                    total += (uint32_t)wmx[k];
+                    before += k < wv ? (uint32_t)wmx[k] : 0u;
+                }
+                if (tid == 0)
+                    bTrAt = total ? __hip_atomic_fetch_add((unsigned long long GAS*)(gp(c.trace_n) +
+                                                                                     ((c.lp0 + r) & ((1u << c.rep_lg) - 1u))),
+                                                           (unsigned long long)total, __ATOMIC_RELAXED,
+                                                           __HIP_MEMORY_SCOPE_AGENT)
+                                  : 0ull;
+                __syncthreads();
+                tr_at = bTrAt + before;
+            }
+        }
         BT(bt4);
         // the prefix for real: other nodes' hash terms, the sends' records
-        const uint32_t K = bK;
         if (!K) continue;  // (uniform)
         {
             const uint32_t node = (c.lp0 + r) >> c.rep_lg;
             uint64_t h = 0;
             uint32_t sm[6] = {0, 0, 0, 0, 0, 0}, dir = 0;
             int64_t fin = INT64_MIN, last = INT64_MIN;
-            for (uint32_t i = tid; i < K; i += TW_BAT_T) {
-                const DueX x = i == tid ? x0 : due_exec(c, bp, r, bSet, ea[i], eb[i]);
+            for (uint32_t i = TR ? i0 : tid; i < (TR ? i1 : K); i += TR ? 1u : TW_BAT_T) {
+                // (the thread's first record is kept from the dry run; TR: unless it traces)
+                [[maybe_unused]] uint32_t ntr = 0;
+                const DueX x = (TR ? i == tid && !ntr0 : i == tid)
+                                   ? x0
+                                   : due_exec<TR>(c, bp, r, bSet, ea[i], eb[i], tr_at, TR ? &ntr : nullptr);
+                if constexpr (TR) tr_at += ntr;
                 dir |= due_effects(c, wid, node, x);
                 h += x.h;
                 sm[0] += x.dl; sm[1] += x.ud; sm[2] += x.dr; sm[3] += x.ev; sm[4] += x.th; sm[5] += x.sq;

@@ -62,9 +62,10 @@
 //
 // Out of scope: TRACE records of node-partitioned contexts (tw_lp_load:
 // tw_set_trace refuses them -- one replica's nodes spread over contexts),
-// records of tw_lp_batch (a traced LPB run keeps its due records on the
-// lanes' chains instead), a job-wide reduction over ranks, chunking the
-// partition path's scratch over several passes.
+// a job-wide reduction over ranks, chunking the partition path's scratch over
+// several passes.  (A traced LPB run keeps its due records on the lanes'
+// chains, or, with tw_set_trace_batch, has tw_lp_batch<true> record them into
+// the same buffer under the same counter: this pass reads either alike.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

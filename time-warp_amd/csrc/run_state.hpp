@@ -209,6 +209,9 @@ struct LpMode {
     bool heavy_ok = false;          // some node's inbox can exceed TW_LIGHT (tw_lp_due runs)
     bool has_ph1 = false;           // two-phase windows (Dev::phase)
     bool fresh = false;             // tw_reset since the last batched-LP tw_run: every counter is 0
+    // tw_set_trace_batch (off after every load), and its value at the last
+    // tw_reset: what lp_window_start launches while tracing is on
+    bool trace_bat = false, trace_bat_run = false;
     uint64_t windows = 0, ticks = 0;  // of the last batched-LP tw_run; outlive loads, like the sweeps' counts
     uint4* foreign = nullptr;       // [out_cap][2]
     uint32_t* n_foreign = nullptr;

@@ -47,6 +47,9 @@ TW_HIDDEN int sh_prefix_stats(tw_shard* c, int64_t* t0, uint64_t* events, uint64
 TW_HIDDEN int sh_prefix_clean_stats(tw_shard* c, uint32_t* claimed, uint64_t* rows_skipped, uint64_t* bytes_stored,
                                     uint32_t* verified, uint64_t* audit);
 TW_HIDDEN int sh_set_trace(tw_shard* c, uint32_t cap);
+// batched LP, tracing on: tw_lp_batch<true> runs the due runs' batchable prefixes
+// and records their TRACEs (off: they stay on the chain); from the next sh_reset
+TW_HIDDEN int sh_set_trace_batch(tw_shard* c, int on);
 TW_HIDDEN int sh_read_trace(tw_shard* c, uint32_t replica, tw_trace_rec* out, size_t cap, uint64_t* n_emitted);
 // tw_measure on one shard: sh_measure_state is its state check alone
 // (TW_ERR_STATE nothing loaded / tracing off, TW_ERR_INVALID node-partitioned

@@ -33,7 +33,7 @@ EXPORTS = ["tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_ru
            "tw_lp_tick_end", "tw_lp_progress", "tw_lp_run_windows", "tw_lpb_load", "tw_lpb_windows",
            "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms", "tw_set_sweep", "tw_sweep_stats",
            "tw_set_prefix", "tw_prefix_stats", "tw_set_measure_keys", "tw_measure_phases_ms",
-           "tw_prefix_clean_stats"]
+           "tw_prefix_clean_stats", "tw_set_trace_batch"]
 GEOMETRIES = ("dense", "sparse", "half", "wave", "lp", "narrow", "lpb", "compact")  # TW_GEO_* order
 
 # tw_trace_rec (include/timewarp.h)
@@ -94,6 +94,9 @@ def load_library(path: Optional[str] = None):
     lib.tw_lp_inject.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64)]
     lib.tw_lp_results.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     lib.tw_set_trace.argtypes = [C.c_void_p, C.c_uint32]
+    if hasattr(lib, "tw_set_trace_batch"):  # (an older in-tree build under TW_LIB lacks it)
+        lib.tw_set_trace_batch.argtypes = [C.c_void_p, C.c_int]
+        lib.tw_set_trace_batch.restype = C.c_int
     lib.tw_read_trace.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
     lib.tw_tie_audit.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint32, C.POINTER(TwStats)]
     lib.tw_set_counter_base.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
@@ -413,11 +416,21 @@ class Engine:
     def set_trace(self, cap: int) -> "Engine":
         """Record up to `cap` TRACE records per replica from the next reset on
         (0: off).  Replica geometries and "lpb" contexts record; a traced lpb
-        run keeps every due record on its node's chain (lpb_batch() reports
-        batched == 0), so it is slower than an untraced one.  A node-partitioned
-        context (tw_lp_load) answers ERR_INVALID."""
+        run by default keeps every due record on its node's chain (lpb_batch()
+        reports batched == 0), so it is slower than an untraced one:
+        set_trace_batch(True) keeps the batch on.  A node-partitioned context
+        (tw_lp_load) answers ERR_INVALID."""
         _check(self.lib.tw_set_trace(self.ctx, int(cap)), "tw_set_trace")
         self._trace_cap = int(cap)
+        return self
+
+    def set_trace_batch(self, on: bool = True) -> "Engine":
+        """An "lpb" context with tracing on: keep the data-parallel batch of
+        the heavy nodes' due records running, in the variant that records
+        their TRACEs (tw_set_trace_batch), from the next reset on.  Off after
+        every load; traces, measures, results and hashes are the same either
+        way.  ERR_STATE before a load, ERR_INVALID for any other geometry."""
+        _check(self.lib.tw_set_trace_batch(self.ctx, 1 if on else 0), "tw_set_trace_batch")
         return self
 
     def trace(self, replica: int, cap: int = 1 << 20):

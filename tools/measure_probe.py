@@ -7,9 +7,9 @@ device's per-replica entries of the sample must equal measure_reference.
 
 --geometry lpb runs the batch in the batched logical-process mode (a power of
 two of at most 32768 replicas per GPU): its traced run keeps every due record on
-the node's chain (tw_lp_batch is off while tracing is on), and Engine.trace
-returns a replica's records in canonical order, so the host sample is compared
-as sorted tuples.
+the node's chain (tw_lp_batch is off while tracing is on) unless --trace-batch
+turns Engine.set_trace_batch on, and Engine.trace returns a replica's records in
+canonical order, so the host sample is compared as sorted tuples.
 
 --max-keys N raises the context's key limit (Engine.set_measure_keys): replicas
 with more than 2,048 keys of the round trip (senders x messages > 1,024) then
@@ -20,7 +20,8 @@ message count: --senders 256 --msgs 1000 --replicas 256 --geometry lpb
 --max-keys 524288 --host-sample 2.
 
 usage: python tools/measure_probe.py [--senders 8] [--msgs 40] [--replicas 65536] [--geometry lpb]
-                                     [--max-keys N] [--host-sample 256] [--out profiles/measure/probe.log]"""
+                                     [--trace-batch] [--max-keys N] [--host-sample 256]
+                                     [--out profiles/measure/probe.log]"""
 import argparse
 import os
 import sys
@@ -42,8 +43,12 @@ ap.add_argument("--replicas", type=int, default=65536)
 ap.add_argument("--host-sample", type=int, default=256)
 ap.add_argument("--max-keys", type=int, default=0, help="Engine.set_measure_keys (default: the library's 2048)")
 ap.add_argument("--geometry", default=None, help="Engine.load's geometry (default: the library's choice)")
+ap.add_argument("--trace-batch", action="store_true",
+                help="lpb: the traced run with Engine.set_trace_batch on (tw_lp_batch<true> records the due runs)")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "measure", "probe.log"))
 a = ap.parse_args()
+if a.trace_batch and a.geometry != "lpb":
+    ap.error("--trace-batch needs --geometry lpb")
 
 S, M, R = a.senders, a.msgs, a.replicas
 cap = 4 * S * M  # four measure events per message
@@ -81,7 +86,10 @@ with Engine(0) as e:
         batched, due = e.lpb_batch()
         say(f"lpb untraced: event kernels {st.kernel_ms:.1f} ms, tw_run wall {st.wall_ms:.1f} ms; {due} due records, "
             f"{batched} of them run by tw_lp_batch")
-    e.set_trace(cap).reset().run()
+    e.set_trace(cap)
+    if a.trace_batch:
+        e.set_trace_batch(True)
+    e.reset().run()
     e.reset()
     st = e.run()
     say(f"hotspot {S} senders x {M} messages x {R} replicas, geometry {e.geometry()}: {st.events} events, "
@@ -89,7 +97,8 @@ with Engine(0) as e:
         f"({cap * R * 32 / 2**30:.2f} GiB)")
     if a.geometry == "lpb":
         batched, due = e.lpb_batch()
-        say(f"lpb: {due} due records, {batched} of them run by tw_lp_batch (off while tracing is on)")
+        how = "tw_lp_batch<true>: set_trace_batch on" if a.trace_batch else "off while tracing is on"
+        say(f"lpb: {due} due records, {batched} of them run by tw_lp_batch ({how})")
     # device path: every replica, with the per-replica array
     for i in range(3):
         t0 = time.perf_counter()
