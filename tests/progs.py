@@ -518,3 +518,43 @@ def payload_prog(value: int):
     c.trace(TAG_TS, 0)
     c.end()
     return single(p, f"payload_{value}")
+
+
+# ------------------------------------------------ listeners (found by netsoup)
+def owned_listener_two_owners():
+    """An owned listener is released when its owner dies (TW_OP_LISTEN, b = 1:
+    token-ring's `serve` thread, examples/token-ring/Main.hs:116-127, whose
+    killThread ends the serving), and only then: `first` binds node 0 owned,
+    `second` binds it again over that, owned too, and dies at 2 µs -- the port
+    is closed.  `first` dies at 6 µs: it owns nothing any more, so its death
+    must change nothing, and main's message at 10 µs finds no listener
+    (undeliverable).  An engine that records every dying once-owner as the
+    one that released the node, and compares the current owner with the last
+    record, has the port open again after `first` died: the message is
+    delivered.  Reduced from netsoup seed 12, replica 53 (a daemon and an
+    inline handler that re-binds the daemon's node)."""
+    p = Program()
+    K = p.kind("msg")
+    lset = p.listener_set({"msg": "on_msg"})
+    c = p.function("main")                       # node 1
+    c.seti(0, 0).fork_("first", node_reg=0, scratch=1)
+    c.wait(for_(10))
+    c.seti(0, 7).link(1, 0).send(1, K, 0)
+    c.end()
+    c = p.function("first")                      # node 0
+    c.listen(lset, owned=True)
+    c.fork_("second")
+    c.wait(for_(5))
+    c.end()
+    c = p.function("second")
+    c.listen(lset, owned=True)
+    c.wait(for_(2))
+    c.end()
+    c = p.function("on_msg")
+    cp(c, 1)
+    c.end()
+    img = p.finalize()
+    topo = Topology.from_out_lists(2, [[], [0]])
+    scn = Scenario(name="owned_listener_two_owners", image=img, topo=topo, n_replicas=1, main_pc=img.pc_of("main"),
+                   main_node=1, max_slots=16, queue_capacity=64, run_capacity=16)
+    return scn, dict(delivered=0, undeliverable=1, cps=[], final_t=12)

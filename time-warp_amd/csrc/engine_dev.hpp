@@ -1393,10 +1393,24 @@ struct Lane {
     // invalidation, slot freed; the caller stores the header quad.
     __device__ __forceinline__ void rel_bind(const Th& th) {
         // an owned listener (token-ring `serve`) is released when its thread
-        // dies: recorded with a store, no read (DELIVER compares the owner)
+        // dies: recorded with a store (DELIVER compares the owner).  Only the
+        // node's current owner releases: a thread whose binding another
+        // LISTEN has replaced since must not overwrite the record of that
+        // later owner's death, which would bind the node again
+        // (progs.owned_listener_two_owners).  The read is paid by threads
+        // that bound with owned = 1 alone, once, as they die
         if (th_flags(th) & F_OWNS) {
-            gp(c.bind_rel)[bix(th.w1)] = th.w2;
-            if constexpr (LP) ds(DW_BREL, th.w2);
+            uint32_t own;
+            if constexpr (LP) {
+                own = dg(DW_BOWN);
+            } else {
+                own = gp(c.bind_own)[bix(th.w1)];
+                tw_vm_drain();
+            }
+            if (own == th.w2) {
+                gp(c.bind_rel)[bix(th.w1)] = th.w2;
+                if constexpr (LP) ds(DW_BREL, th.w2);
+            }
         }
     }
     __device__ __forceinline__ void die_prep(Th& th, uint32_t slot) {

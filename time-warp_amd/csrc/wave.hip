@@ -649,7 +649,9 @@ struct Wave {
     // Thread ends: owned listener released, refs invalidated, slot freed; the
     // header quad is stored by the caller.
     __device__ __forceinline__ void die(URec& th, uint32_t slot) {
-        if (u_flags(th) & F_OWNS) st32(gp(dv->bind_rel) + ix(th.w1), th.w2);
+        // (only the node's current owner releases it: Lane::rel_bind)
+        if ((u_flags(th) & F_OWNS) && rfl(gp(dv->bind_own)[ix(th.w1)]) == th.w2)
+            st32(gp(dv->bind_rel) + ix(th.w1), th.w2);
         th.w2 = 0xFFFFFFFFu;
         th.w3 = 0;
         free_slot(slot);
