@@ -694,6 +694,58 @@ int tw_lp_inject(tw_ctx* ctx, const tw_lp_record* recs, size_t n, int64_t* next_
  * over its devices and ranks). */
 int tw_lp_results(tw_ctx* ctx, tw_replica_result* agg, uint64_t* node_hashes, size_t n_nodes);
 
+/* ---- TRACE records and latency measures of a node-partitioned context
+ * tw_set_trace, tw_read_trace and tw_measure keep refusing a tw_lp_load context
+ * (TW_ERR_INVALID); this family serves it.  The context is one replica whose
+ * nodes are lanes; a record claims its index from one counter per shard, and
+ * the lanes of a wavefront that trace together claim once (one returning
+ * atomic per wavefront), so the kept records are in no execution order.
+ *
+ * tw_lp_set_trace: keep track of up to cap TRACE records of the context from
+ * the next tw_reset on (0 = off: releases the buffers); survives tw_reset, is
+ * dropped by the next tw_lp_load.  Every shard of a tw_create(devices, n)
+ * context allocates cap * 32 + 8 bytes of HBM.  cap is 32-bit, like
+ * tw_set_trace's: record indices, the join's kept counts and its key limit are
+ * 32-bit words on the device.  TW_ERR_STATE before a load, TW_ERR_INVALID for a
+ * tw_load or tw_lpb_load context, TW_ERR_OOM when a buffer cannot be had (the
+ * context stays usable, tracing off).  While tracing is on, the data-parallel
+ * batch of the heavy nodes' due records stays off.
+ *
+ * Truncation does not depend on the shard count: with E the records the
+ * context emitted (the sum over its shards), the context is truncated iff
+ * E > cap; when E <= cap every shard kept everything. */
+int tw_lp_set_trace(tw_ctx* ctx, uint32_t cap);
+
+/* The context's records, all shards merged, sorted by (t, node, tag, val) --
+ * tw_read_trace's canonical order for tw_lpb_load contexts; node is the global
+ * node id.  Blocks until the last run has finished; copies min(cap, E, trace
+ * cap) records and stores E in *n_emitted.  A truncated context: which records
+ * were kept is unspecified, E is exact.  A rank of a tw_create_rank job with
+ * more than one rank gets the records of its own node block only, and E is
+ * that block's; with several contexts in one process driven by the caller
+ * (tw_lp_window / tw_lp_tick), each context is read on its own.
+ * TW_ERR_STATE before a load or with tracing off, TW_ERR_INVALID for any other
+ * kind of context. */
+int tw_lp_read_trace(tw_ctx* ctx, tw_trace_rec* out, size_t cap, uint64_t* n_emitted);
+
+/* tw_measure's join over the context's one replica, with the same classes and
+ * the same histogram: *out (or NULL) and hist[spec->n_bins] (or NULL).  The
+ * shards' records are gathered into one buffer on the first shard's device
+ * (allocated for the call: E * 32 bytes) and joined there, so an id whose two
+ * records sit on different shards is a pair.  A truncated context gives
+ * truncated == 1 and nothing else; otherwise truncated is 0.
+ * tw_set_measure_keys governs the key limit as for tw_measure: up to
+ * TW_MEASURE_MAX_KEYS matching records are joined in LDS, more take the
+ * partition path up to the setting, and above it the call returns
+ * TW_ERR_INVALID with nothing written.  tw_measure_ms and tw_measure_phases_ms
+ * report its kernels.
+ * TW_ERR_STATE before a load or with tracing off; TW_ERR_INVALID for any other
+ * kind of context, for a bad spec, and for a rank of a tw_create_rank job with
+ * more than one rank (there is no job-wide gather; a one-rank job works);
+ * TW_ERR_OOM when the gather buffer cannot be had (nothing written, the
+ * context stays usable). */
+int tw_lp_measure(tw_ctx* ctx, const tw_measure_spec* spec, tw_measure_out* out, uint64_t* hist);
+
 /* ---- batched node-partitioned mode (intra-replica parallelism)
  * R replicas of a scenario whose nodes interact only through sends of at
  * least lookahead_us (plus forks onto other nodes issued before any node runs

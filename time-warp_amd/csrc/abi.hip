@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/timewarp.h"
+#include "lp_trace_plan.hpp"
 #include "measure_combine.hpp"
 #include "shard.hpp"
 #include "tw_dev.hpp"
@@ -84,6 +85,7 @@ struct tw_ctx {
     double measure_phase_ms[MEASURE_PHASES] = {};  // ... by kernel (tw_measure_phases_ms): the slowest shard's
     // tw_set_measure_keys, and the testing hook TW_TEST_MEASURE (test_hook_init)
     MeasureCfg measure_cfg{TW_MEASURE_MAX_KEYS, TW_MEASURE_MAX_KEYS, 1024};
+    uint32_t lp_trace_cap = 0;  // tw_lp_set_trace: records the context keeps track of (each shard holds as many)
 };
 
 namespace {
@@ -946,6 +948,127 @@ int tw_lp_results(tw_ctx* c, tw_replica_result* agg, uint64_t* node_hashes, size
             }
         }
     }
+    return TW_OK;
+}
+
+// ---- TRACE records of a node-partitioned context (lp_trace_plan.hpp holds
+// the counting rule, the gather offsets and the merge).  Every shard keeps up
+// to `cap` records of its own node block; the context sums the counts.
+int tw_lp_set_trace(tw_ctx* c, uint32_t cap) {
+    if (!c) return TW_ERR_INVALID;
+    for (tw_shard* s : c->sh) {  // (checked before any shard changes)
+        int rc = sh_lp_kind(s);
+        if (rc) return rc;
+    }
+    for (tw_shard* s : c->sh) {
+        int rc = sh_lp_set_trace(s, cap);
+        if (rc) {
+            for (tw_shard* u : c->sh) (void)sh_lp_set_trace(u, 0);  // all or none: tracing off
+            c->lp_trace_cap = 0;
+            return rc;
+        }
+    }
+    c->lp_trace_cap = cap;
+    return TW_OK;
+}
+
+namespace {
+// the shards' emitted counts, each read behind its shard's last run
+int lp_trace_counts(tw_ctx* c, std::vector<uint64_t>& counts) {
+    counts.assign(c->sh.size(), 0);
+    for (size_t i = 0; i < c->sh.size(); ++i) {
+        int rc = sh_lp_trace_count(c->sh[i], &counts[i]);
+        if (rc) return rc;
+    }
+    return TW_OK;
+}
+}  // namespace
+
+int tw_lp_read_trace(tw_ctx* c, tw_trace_rec* out, size_t cap, uint64_t* n_emitted) {
+    if (!c || (cap && !out)) return TW_ERR_INVALID;
+    std::vector<uint64_t> counts;
+    int rc = lp_trace_counts(c, counts);
+    if (rc) return rc;
+    const LpTracePlan p = lp_trace_plan(counts.data(), counts.size(), c->lp_trace_cap);
+    const size_t k = lp_trace_clip(p.emitted, c->lp_trace_cap, cap);
+    if (k) {
+        const size_t n = c->sh.size();
+        std::vector<std::vector<tw_trace_rec>> recs(n);
+        std::vector<const tw_trace_rec*> lists(n);
+        for (size_t i = 0; i < n; ++i) {
+            recs[i].resize((size_t)p.kept[i]);
+            rc = sh_lp_trace_fetch(c->sh[i], recs[i].data(), recs[i].size());
+            if (rc) return rc;
+            lp_trace_sort(recs[i].data(), recs[i].size());  // (claim order says nothing)
+            lists[i] = recs[i].data();
+        }
+        std::vector<tw_trace_rec> merged(k);
+        if (lp_trace_merge(lists.data(), p.kept.data(), n, merged.data(), k) != k) return TW_ERR_STATE;
+        std::memcpy(out, merged.data(), k * sizeof(tw_trace_rec));
+    }
+    if (n_emitted) *n_emitted = p.emitted;
+    return TW_OK;
+}
+
+// The join over the context's one replica: the shards' kept records are
+// gathered into one buffer on shard 0's device (device-to-device or peer
+// copies on shard 0's stream, after every shard's stream was synchronised by
+// the count read), and tw_measure's pass runs there over one replica of E
+// records.  The buffer lives for the call; the caller's buffers are written
+// only on success.
+int tw_lp_measure(tw_ctx* c, const tw_measure_spec* spec, tw_measure_out* out, uint64_t* hist) {
+    if (!c || !spec) return TW_ERR_INVALID;
+    for (tw_shard* s : c->sh) {
+        int rc = sh_lp_trace_state(s);
+        if (rc) return rc;
+    }
+    if (!measure_spec_ok(spec)) return TW_ERR_INVALID;
+    if (c->world != (int)c->sh.size()) return TW_ERR_INVALID;  // a rank of a larger job: no job-wide gather
+    std::vector<uint64_t> counts;
+    int rc = lp_trace_counts(c, counts);
+    if (rc) return rc;
+    const LpTracePlan p = lp_trace_plan(counts.data(), counts.size(), c->lp_trace_cap);
+    tw_measure_out tot;
+    measure_empty(&tot);
+    std::vector<uint64_t> h(spec->n_bins, 0);
+    double ms = 0.0, phase[MEASURE_PHASES] = {};
+    if (p.truncated) {
+        tot.truncated = 1;  // (contributes nothing else; no gather)
+    } else if (p.emitted) {
+        struct Buf {
+            void* p = nullptr;
+            ~Buf() {
+                if (p) (void)hipFree(p);
+            }
+        } buf;
+        const int dev0 = c->dev[0];
+        hipStream_t st = sh_stream(c->sh[0]);
+        HIPCHK_A(hipSetDevice(dev0));
+        // the records, then the replica's emitted count
+        if (hipMalloc(&buf.p, (size_t)p.emitted * 32 + 8) != hipSuccess) {
+            (void)hipGetLastError();  // (not sticky: the context stays usable)
+            return TW_ERR_OOM;
+        }
+        for (size_t i = 0; i < c->sh.size(); ++i) {
+            if (!p.kept[i]) continue;
+            char* dst = (char*)buf.p + (size_t)p.off[i] * 32;
+            const size_t bytes = (size_t)p.kept[i] * 32;
+            if (c->dev[i] == dev0)
+                HIPCHK_A(hipMemcpyAsync(dst, sh_lp_trace_dev(c->sh[i]), bytes, hipMemcpyDeviceToDevice, st));
+            else
+                HIPCHK_A(hipMemcpyPeerAsync(dst, dev0, sh_lp_trace_dev(c->sh[i]), c->dev[i], bytes, st));
+        }
+        uint64_t* d_n = (uint64_t*)((char*)buf.p + (size_t)p.emitted * 32);
+        HIPCHK_A(hipMemcpyAsync(d_n, &p.emitted, 8, hipMemcpyHostToDevice, st));
+        rc = measure_run(dev0, st, (const uint4*)buf.p, d_n, 1, (uint32_t)p.emitted, spec, c->measure_cfg, &tot, h.data(),
+                         nullptr, &ms, phase);
+        HIPCHK_A(hipStreamSynchronize(st));  // (before the buffer goes)
+        if (rc) return rc;
+    }
+    if (out) *out = tot;
+    if (hist) std::memcpy(hist, h.data(), (size_t)spec->n_bins * 8);
+    c->measure_ms = ms;
+    std::copy(phase, phase + MEASURE_PHASES, c->measure_phase_ms);
     return TW_OK;
 }
 

@@ -175,7 +175,8 @@ static bool ordered_ties(const tw_shard* c) {
 // is: what load_common registers and what launch_run picks from.
 //   LP: the work list walked grid-stride (gs: many lanes, few listed), the
 //   batched device loop's per-replica windows (prw), TRACE records kept (tr:
-//   tw_set_trace on, batched LP only; the others compile Lane::trace_rec out);
+//   tw_set_trace on a batched LP context, tw_lp_set_trace on a node-partitioned
+//   one; the others compile Lane::trace_rec out);
 //   replicas: the fork-in-place variant (ip: Lane::fork_in_place).
 struct Variant {
     bool gs, prw, ip, tr;
@@ -218,7 +219,7 @@ static void launch_run(tw_shard* c, hipStream_t st, int64_t t_end, uint64_t limi
     uint32_t blocks = (grid && !G::LP) ? grid : (uint32_t)((c->d.R + G::WG - 1) / G::WG);
     Variant v{false, false, use_ip<G>(c), false};
     if constexpr (G::LP) {
-        v = Variant{blocks > c->lp_grid, c->d.rw && c->d.win, false, c->lpm.lpb && c->d.trace_cap != 0};
+        v = Variant{blocks > c->lp_grid, c->d.rw && c->d.win, false, c->d.trace_cap != 0};
         if (v.gs) blocks = c->lp_grid;
     }
     each_kernel<G>([&](RunKernel k, Variant kv) {
@@ -1867,6 +1868,72 @@ int sh_read_trace(tw_shard* c, uint32_t replica, tw_trace_rec* out, size_t cap, 
     }
     return TW_OK;
 }
+
+// ---- node-partitioned contexts (tw_lp_set_trace ...): one replica, whose
+// records of this shard's node block sit as [n][1][2] quads under one counter
+int sh_lp_kind(tw_shard* c) {
+    if (!c) return TW_ERR_INVALID;
+    if (!c->loaded) return TW_ERR_STATE;
+    return (!c->lpm.lp || c->lpm.lpb) ? TW_ERR_INVALID : TW_OK;
+}
+
+int sh_lp_trace_state(tw_shard* c) {
+    int rc = sh_lp_kind(c);
+    if (rc) return rc;
+    if (!c->d.trace || !c->d.trace_cap || !c->d.trace_n) return TW_ERR_STATE;
+    return TW_OK;
+}
+
+int sh_lp_set_trace(tw_shard* c, uint32_t cap) {
+    if (!c) return TW_ERR_INVALID;
+    if (!c->loaded) return TW_ERR_STATE;
+    if (!c->lpm.lp || c->lpm.lpb) return TW_ERR_INVALID;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    trace_release(c->d);  // (Dev is the tick graph's key: the next tick captures the other variant)
+    if (cap) {
+        if (hipMalloc(&c->d.trace, (size_t)cap * 32) != hipSuccess || hipMalloc(&c->d.trace_n, 8) != hipSuccess) {
+            (void)hipGetLastError();  // (not sticky: the context stays usable, tracing off)
+            trace_release(c->d);
+            return TW_ERR_OOM;
+        }
+        HIPCHK(hipMemsetAsync(c->d.trace_n, 0, 8, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->d.trace_cap = cap;
+    }
+    return TW_OK;
+}
+
+int sh_lp_trace_count(tw_shard* c, uint64_t* n) {
+    int rc = sh_lp_trace_state(c);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(n, c->d.trace_n, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return TW_OK;
+}
+
+int sh_lp_trace_fetch(tw_shard* c, tw_trace_rec* out, size_t k) {
+    int rc = sh_lp_trace_state(c);
+    if (rc) return rc;
+    if (k > c->d.trace_cap) return TW_ERR_INVALID;
+    if (!k) return TW_OK;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<uint4> buf(2 * k);
+    HIPCHK(hipMemcpyAsync(buf.data(), c->d.trace, k * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < k; ++i) {
+        const uint4 a = buf[2 * i], b = buf[2 * i + 1];
+        out[i].t = (int64_t)(((uint64_t)a.y << 32) | a.x);
+        out[i].val = (int64_t)(((uint64_t)b.y << 32) | b.x);
+        out[i].node = a.z;
+        out[i].tag = a.w;
+    }
+    return TW_OK;
+}
+
+const uint4* sh_lp_trace_dev(tw_shard* c) { return c->d.trace; }
+hipStream_t sh_stream(tw_shard* c) { return c->stream; }
 
 int sh_measure_state(tw_shard* c) {
     if (!c) return TW_ERR_INVALID;

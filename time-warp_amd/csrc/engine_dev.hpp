@@ -1473,10 +1473,36 @@ struct Lane {
     // one returning atomic per record; a wave's 64 lanes are 64 replicas of one
     // node, so its atomics fall on 512 contiguous bytes.  The count goes on
     // past the cap (tw_read_trace reports it); records are kept while the
-    // claimed index is below it, in claim order -- no execution order
+    // claimed index is below it, in claim order -- no execution order.
+    // A node-partitioned context (tw_lp_set_trace; rep_lg == 0, a scalar
+    // branch) has one replica and so one counter word for every lane of every
+    // wave: there the lanes that run this TRACE together (the exec mask: the
+    // call sits under the per-lane condition) claim once per wave -- the
+    // first of them adds their number with one returning atomic, the base is
+    // broadcast, and a lane's index is the base plus its rank in the mask
     __device__ __forceinline__ void trace_rec(uint32_t node, int32_t tag, int64_t val) {
         if constexpr (LP) {
             if constexpr (TR) {
+                if (c.rep_lg == 0) {
+                    const uint64_t act = __builtin_amdgcn_ballot_w64(true);
+                    const uint32_t rank =
+                        __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0u));
+                    unsigned long long base = 0;
+                    if (rank == 0)
+                        base = __hip_atomic_fetch_add((unsigned long long GAS*)gp(c.trace_n),
+                                                      (unsigned long long)__builtin_popcountll(act), __ATOMIC_RELAXED,
+                                                      __HIP_MEMORY_SCOPE_AGENT);
+                    // (the first active lane is the one of rank 0)
+                    const uint32_t blo = __builtin_amdgcn_readfirstlane((uint32_t)base);
+                    const uint32_t bhi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
+                    const unsigned long long n = (((unsigned long long)bhi << 32) | blo) + rank;
+                    if (n < c.trace_cap) {
+                        uint4 GAS* q = gp(c.trace) + (size_t)n * 2;
+                        q[0] = make_uint4((uint32_t)now, (uint32_t)((uint64_t)now >> 32), node, (uint32_t)tag);
+                        q[1] = make_uint4((uint32_t)val, (uint32_t)((uint64_t)val >> 32), 0u, 0u);
+                    }
+                    return;
+                }
                 const uint32_t rh = rho();
                 const unsigned long long n = __hip_atomic_fetch_add(
                     (unsigned long long GAS*)(gp(c.trace_n) + rh), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -60,9 +60,10 @@
 // histogram 4096 x 4 B = 16 KiB, a few accumulators: ~50.1 KiB static, under
 // the 64 KiB a workgroup may hold; 3 workgroups per CU of the 160 KiB.
 //
-// Out of scope: TRACE records of node-partitioned contexts (tw_lp_load:
-// tw_set_trace refuses them -- one replica's nodes spread over contexts),
-// a job-wide reduction over ranks, chunking the partition path's scratch over
+// A node-partitioned context (tw_lp_load; tw_set_trace refuses it) comes here
+// through tw_lp_measure (abi.hip): its shards' records gathered into one
+// buffer, one replica (R == 1) of E records, counted by tw_measure_count_one.
+// Out of scope: a job-wide reduction over ranks, chunking the partition path's scratch over
 // several passes.  (A traced LPB run keeps its due records on the lanes'
 // chains, or, with tw_set_trace_batch, has tw_lp_batch<true> record them into
 // the same buffer under the same counter: this pass reads either alike.)
@@ -117,6 +118,45 @@ __global__ __launch_bounds__(MS_WG) void tw_measure_count(const uint4* __restric
     }
     cnt[r] = k;
     if (k > MS_KEYS) atomicOr(err, 1u);
+}
+
+// R == 1 (tw_lp_measure: a node-partitioned context's one replica, of
+// millions of records): the same count with a grid-stride walk over n, 32 B
+// apart per lane, reduced per wave and per workgroup, one atomic per workgroup
+// on cnt[0] (zeroed by the host).  The workgroup whose add carries the count
+// over MS_KEYS sets the error word: exactly one does.
+__global__ __launch_bounds__(MS_WG) void tw_measure_count_one(const uint4* __restrict__ trace,
+                                                              const uint64_t* __restrict__ emitted, uint32_t cap,
+                                                              uint32_t tag_from, uint32_t tag_to,
+                                                              uint32_t* __restrict__ cnt, uint32_t* err,
+                                                              tw_measure_out* total) {
+    __shared__ uint32_t s_k[MS_WG / 64];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        total->min_us = INT64_MAX;
+        total->max_us = INT64_MIN;
+    }
+    const uint64_t em = emitted[0];  // (uniform: every return below is the whole grid's)
+    if (em > cap) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) cnt[0] = MS_TRUNC;
+        return;
+    }
+    const uint32_t kept = (uint32_t)em;
+    uint32_t k = 0;
+    for (uint64_t n = (uint64_t)blockIdx.x * MS_WG + threadIdx.x; n < kept; n += (uint64_t)gridDim.x * MS_WG) {
+        const uint32_t tag = trace[(size_t)n * 2].w;
+        k += (tag == tag_from || tag == tag_to) ? 1u : 0u;
+    }
+    for (int o = 32; o > 0; o >>= 1) k += __shfl_down(k, o, 64);
+    if ((threadIdx.x & 63u) == 0) s_k[threadIdx.x >> 6] = k;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t w = 0;
+        for (uint32_t i = 0; i < MS_WG / 64; ++i) w += s_k[i];
+        if (w) {
+            const uint32_t old = atomicAdd(&cnt[0], w);  // (<= kept < 2^32: no wrap)
+            if (old <= MS_KEYS && old + w > MS_KEYS) atomicOr(err, 1u);
+        }
+    }
 }
 
 struct MsKeys {
@@ -635,9 +675,17 @@ int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64
     uint32_t* d_cnt = (uint32_t*)(base + o_cnt);
 
     MSCHK(hipMemsetAsync(base, 0, o_per, stream));
+    if (R == 1) MSCHK(hipMemsetAsync(d_cnt, 0, 4, stream));
     MSCHK(hipEventRecord(res.ev[0], stream));
-    tw_measure_count<<<(R + MS_WG - 1) / MS_WG, MS_WG, 0, stream>>>(trace, emitted, R, cap, spec->tag_from,
-                                                                   spec->tag_to, d_cnt, d_err, d_total);
+    if (R == 1) {
+        // one replica: parallel over its records (at most cap of them are read)
+        const uint32_t cgrid = (uint32_t)std::min<uint64_t>(((uint64_t)cap + MS_WG - 1) / MS_WG, 4 * MS_GRID);
+        tw_measure_count_one<<<cgrid, MS_WG, 0, stream>>>(trace, emitted, cap, spec->tag_from, spec->tag_to, d_cnt,
+                                                          d_err, d_total);
+    } else {
+        tw_measure_count<<<(R + MS_WG - 1) / MS_WG, MS_WG, 0, stream>>>(trace, emitted, R, cap, spec->tag_from,
+                                                                       spec->tag_to, d_cnt, d_err, d_total);
+    }
     MSCHK(hipGetLastError());
     MSCHK(hipEventRecord(res.ev[1], stream));
     uint32_t h_err = 0;

@@ -74,6 +74,20 @@ TW_HIDDEN int sh_measure(tw_shard* c, const tw_measure_spec* spec, const Measure
 TW_HIDDEN int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64_t* emitted, uint32_t R,
                           uint32_t cap, const tw_measure_spec* spec, const MeasureCfg& cfg, tw_measure_out* total,
                           uint64_t* hist, tw_measure_out* per, double* kernel_ms, double* phase_ms);
+// tw_lp_set_trace ... on one shard of a node-partitioned context: the shard
+// keeps up to cap records of its node block under one counter.
+// sh_lp_trace_state: TW_ERR_STATE nothing loaded / tracing off, TW_ERR_INVALID
+// any other kind of context; sh_lp_trace_count synchronises the shard's stream
+// and reads the emitted count; sh_lp_trace_fetch copies the first k (<= cap)
+// records out in claim order; sh_lp_trace_dev / sh_stream: what the gather of
+// tw_lp_measure copies from, and the stream it is ordered on
+TW_HIDDEN int sh_lp_kind(tw_shard* c);  // TW_OK: a loaded node-partitioned shard
+TW_HIDDEN int sh_lp_trace_state(tw_shard* c);
+TW_HIDDEN int sh_lp_set_trace(tw_shard* c, uint32_t cap);
+TW_HIDDEN int sh_lp_trace_count(tw_shard* c, uint64_t* n);
+TW_HIDDEN int sh_lp_trace_fetch(tw_shard* c, tw_trace_rec* out, size_t k);
+TW_HIDDEN const uint4* sh_lp_trace_dev(tw_shard* c);
+TW_HIDDEN hipStream_t sh_stream(tw_shard* c);
 TW_HIDDEN int sh_last_launch_ms(tw_shard* c, double* out, size_t cap);
 TW_HIDDEN int sh_prof_read(tw_shard* c, unsigned long long* out, size_t cap, int reset);
 // shape of what a shard holds: replicas its results cover (batched LP: the

@@ -33,7 +33,7 @@ EXPORTS = ["tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_ru
            "tw_lp_tick_end", "tw_lp_progress", "tw_lp_run_windows", "tw_lpb_load", "tw_lpb_windows",
            "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms", "tw_set_sweep", "tw_sweep_stats",
            "tw_set_prefix", "tw_prefix_stats", "tw_set_measure_keys", "tw_measure_phases_ms",
-           "tw_prefix_clean_stats", "tw_set_trace_batch"]
+           "tw_prefix_clean_stats", "tw_set_trace_batch", "tw_lp_set_trace", "tw_lp_read_trace", "tw_lp_measure"]
 GEOMETRIES = ("dense", "sparse", "half", "wave", "lp", "narrow", "lpb", "compact")  # TW_GEO_* order
 
 # tw_trace_rec (include/timewarp.h)
@@ -126,6 +126,12 @@ def load_library(path: Optional[str] = None):
         lib.tw_prefix_clean_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         lib.tw_prefix_clean_stats.restype = C.c_int
+    if hasattr(lib, "tw_lp_set_trace"):  # (an older in-tree build under TW_LIB lacks them)
+        lib.tw_lp_set_trace.argtypes = [C.c_void_p, C.c_uint32]
+        lib.tw_lp_read_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.tw_lp_measure.argtypes = [C.c_void_p, C.POINTER(TwMeasureSpec), C.POINTER(TwMeasureOut), C.c_void_p]
+        for name in ("tw_lp_set_trace", "tw_lp_read_trace", "tw_lp_measure"):
+            getattr(lib, name).restype = C.c_int
     for name in ("tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_run", "tw_set_tie_mode", "tw_load", "tw_reset", "tw_run", "tw_read_results", "tw_read_hashes", "tw_read_final",
                  "tw_last_launch_ms", "tw_lp_load", "tw_lp_window", "tw_lp_take_outbox", "tw_lp_inject",
                  "tw_lp_results", "tw_set_trace", "tw_read_trace", "tw_tie_audit", "tw_set_counter_base",
@@ -489,6 +495,42 @@ class Engine:
         v = C.c_double()
         _check(self.lib.tw_measure_ms(self.ctx, C.byref(v)), "tw_measure_ms")
         return float(v.value)
+
+    # ---- TRACE records of a node-partitioned context (LPEngine; defined here so
+    # that every kind of context answers with the library's status)
+    def lp_set_trace(self, cap: int) -> "Engine":
+        """Keep track of up to `cap` TRACE records of the whole context from the
+        next reset on (tw_lp_set_trace; 0: off).  The context is truncated when
+        it emitted more than `cap`, however many devices it is split over.
+        ERR_STATE before a load, ERR_INVALID for a context that is not
+        node-partitioned."""
+        _check(self.lib.tw_lp_set_trace(self.ctx, int(cap)), "tw_lp_set_trace")
+        self._lp_trace_cap = int(cap)
+        return self
+
+    def lp_trace(self, cap: int = 1 << 20):
+        """(records, emitted): the context's TRACE records of the last run,
+        every device's merged, sorted by (t, node, tag, val) with global node
+        ids (TRACE_DTYPE) -- a canonical order, not an execution order.  A
+        truncated context returns an unspecified `cap` of its records;
+        `emitted` is exact.  A rank of a larger job reads its own nodes'."""
+        buf = np.zeros(cap, TRACE_DTYPE)
+        n = C.c_uint64()
+        _check(self.lib.tw_lp_read_trace(self.ctx, buf.ctypes.data, cap, C.byref(n)), "tw_lp_read_trace")
+        return buf[:min(int(n.value), cap, getattr(self, "_lp_trace_cap", 0))].copy(), int(n.value)
+
+    def lp_measure(self, tag_from: int, tag_to: int, lo_us: int = 0, bin_us: int = 1, n_bins: int = 1):
+        """measure() over the context's one replica (tw_lp_measure): (total,
+        hist).  Records of all devices are joined together; a truncated
+        context gives truncated == 1 and nothing else.  set_measure_keys,
+        measure_ms and measure_phases_ms apply as for measure()."""
+        spec = TwMeasureSpec(tag_from=int(tag_from), tag_to=int(tag_to), n_bins=int(n_bins), reserved=0,
+                             lo_us=int(lo_us), bin_us=int(bin_us))
+        tot = TwMeasureOut()
+        hist = np.zeros(max(int(n_bins), 0), np.uint64)
+        _check(self.lib.tw_lp_measure(self.ctx, C.byref(spec), C.byref(tot), hist.ctypes.data if hist.size else None),
+               "tw_lp_measure")
+        return {f: int(getattr(tot, f)) for f, _ in TwMeasureOut._fields_}, hist
 
     def launch_ms(self) -> np.ndarray:
         buf = np.zeros(1 << 16, np.float64)

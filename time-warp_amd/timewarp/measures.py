@@ -142,6 +142,31 @@ def measure_reference(per_replica_records, emitted, cap: int, spec: dict):
     return total, np.array(hist, dtype=np.uint64), per
 
 
+def first_receipts(records, tag: int, lo_us: int = 0, bin_us: int = 1000, n_bins: int = 16):
+    """The first-receipt distribution of `tag` (gossip's TAG_RUMOR_FIRST: the
+    propagation curve) from canonical records -- LPEngine.lp_trace's, an
+    "lpb" Engine.trace's or the oracle's trace log.  A node counts once, at its
+    earliest record of the tag.  Returns (times, hist): the nodes' first times
+    in ascending order (int64) and the uint64 counts of the bins
+    [lo_us + i * bin_us, lo_us + (i + 1) * bin_us); times outside the bins are
+    in `times` only."""
+    import numpy as np
+
+    if n_bins < 1 or bin_us < 1:
+        raise ValueError("n_bins and bin_us must be >= 1")
+    first: Dict[int, int] = {}
+    for t, node, k, _val in trace_tuples(records):
+        if k == int(tag) and (node not in first or t < first[node]):
+            first[node] = t
+    times = np.array(sorted(first.values()), dtype=np.int64)
+    hist = np.zeros(n_bins, np.uint64)
+    for t in times:
+        b = (int(t) - int(lo_us)) // int(bin_us)
+        if 0 <= b < n_bins:
+            hist[b] += 1
+    return times, hist
+
+
 def trace_tuples(recs) -> list:
     """Engine.trace records (TRACE_DTYPE) or oracle traces -> (t, node, tag, val) tuples."""
     if hasattr(recs, "dtype"):

@@ -571,11 +571,13 @@ def socket_state(n_replicas: int = 1, network_delay=(ms(1), ms(5)), seed_base: i
 # ------------------------------------------------------------------- gossip
 TAG_RUMOR_FIRST = 9      # first receipt of the rumor at a node
 K_RUMOR_PAYLOAD = 7      # forwarding is payload-independent (tie-insensitive by design)
+TAG_RUMOR_SENT = 10      # gossip(message_ids=True): before a send, val = the message's id (its link id)
+TAG_RUMOR_RECV = 11      # ... on every delivery, val = the id the copy carries
 
 
 def gossip(n_nodes: int = 1024, fanout: int = 4, n_replicas: int = 1, network_delay=(ms(1), ms(5)),
            seed: int = 0, start_us: int = sec(1), origin: int = 0, drop_log2: int = 0,
-           near_horizon_us: int = sec(10), fork_strategy: str = "fork") -> Scenario:
+           near_horizon_us: int = sec(10), fork_strategy: str = "fork", message_ids: bool = False) -> Scenario:
     """Config 4: one gossip/broadcast scenario (build-defined; the reference has
     no gossip example — it composes MonadDialog `listen`/`send`, MonadDialog.hs
     :149-271, exactly like examples/ping-pong).
@@ -590,6 +592,15 @@ def gossip(n_nodes: int = 1024, fanout: int = 4, n_replicas: int = 1, network_de
     drawn from mkStdGen(seed); the minimum link delay (1 ms) is the lookahead
     of the node-partitioned engine.  ``fork_strategy="inline"`` runs the
     handler in place in the delivering thread (MonadDialog.hs:114-117).
+
+    ``message_ids=True`` makes every message measurable (the bench/Network
+    PingSent / PingReceived pair): a send is preceded by
+    ``trace(TAG_RUMOR_SENT, id)`` and carries the id as its payload, and the
+    handler opens with ``trace(TAG_RUMOR_RECV, id)`` before the duplicate
+    check.  The id is the link id -- unique per message, since a node forwards
+    once.  Forwarding still ignores the payload, and TAG_RUMOR_FIRST then
+    traces a constant register, so which of several equal-time copies arrives
+    first reaches no output.
     """
     if fork_strategy not in ("fork", "inline"):
         raise ValueError(f"fork_strategy must be 'fork' or 'inline', not {fork_strategy!r}")
@@ -604,16 +615,24 @@ def gossip(n_nodes: int = 1024, fanout: int = 4, n_replicas: int = 1, network_de
     c.nstore(0, 0)                                     # the origin knows the rumor
     c.now(3).nstore(3, 1)
     for k in range(F):
-        c.link(1, k).send(1, K, 0)
+        if message_ids:
+            c.link(1, k).trace(TAG_RUMOR_SENT, 1).send(1, K, 1)
+        else:
+            c.link(1, k).send(1, K, 0)
     c.end()
 
     c = p.function("on_rumor")                        # listener: r0 = payload
     dup = c.label()
+    if message_ids:
+        c.trace(TAG_RUMOR_RECV, 0)
     c.nload(2, 0).jnei(2, 0, dup)                      # already seen -> ignore
     c.seti(2, 1).nstore(2, 0).now(3).nstore(3, 1)
-    c.trace(TAG_RUMOR_FIRST, 0)
+    c.trace(TAG_RUMOR_FIRST, 2 if message_ids else 0)  # (r2 = 1: not the payload of whichever copy came first)
     for k in range(F):
-        c.link(1, k).send(1, K, 0)
+        if message_ids:
+            c.link(1, k).trace(TAG_RUMOR_SENT, 1).send(1, K, 1)
+        else:
+            c.link(1, k).send(1, K, 0)
     c.bind(dup)
     c.end()
 
@@ -658,7 +677,8 @@ def gossip(n_nodes: int = 1024, fanout: int = 4, n_replicas: int = 1, network_de
     table[:, 0, :] = delays[:, None]
     listen = np.full(N, lset + 1, np.uint32)
     return Scenario(
-        name=f"gossip_n{N}" + ("_inline" if fork_strategy == "inline" else ""), image=img, topo=topo, n_replicas=n_replicas,
+        name=f"gossip_n{N}" + ("_inline" if fork_strategy == "inline" else "") + ("_ids" if message_ids else ""),
+        image=img, topo=topo, n_replicas=n_replicas,
         main_pc=img.pc_of("main"), main_node=origin, link_table=table, node_listen=listen,
         max_slots=_capped(8 * N + 64), queue_capacity=_capped(8 * N + 256), run_capacity=_capped(4 * N + 64),
         near_horizon_us=near_horizon_us,
