@@ -653,6 +653,47 @@ typedef struct tw_table_draw {
 } tw_table_draw;
 int tw_draw_link_table(int device, const tw_table_draw* spec, uint32_t* out);
 
+/* ------------------------------------------------ live delays: drawn at the send
+ * The reference's network nastiness as it is written: a function evaluated per
+ * message with a live generator (examples/token-ring/Main.hs:73-77 draws
+ * U[1000, 5000] µs for every token from one mkStdGen, in the order in which
+ * the sends happen).  Replica r owns one StdGen, mkStdGen(seed_base + r) with
+ * r its index in the whole batch (a context over several devices seeds by that
+ * index, so the split is invisible; a tw_create_rank context counts within the
+ * rank's own block: give each rank its seed_base).  It is seeded by this call
+ * and by every tw_reset, and persists across tw_run calls: a run cut at t_end
+ * or max_events and continued keeps drawing where it stopped.  At a SEND over
+ * link l, in the replica's execution order:
+ *   kind[l] == 1  the delay is lo[l];
+ *   kind[l] == 2  the delay is lo + (next - 1) mod k with k = hi - lo + 1, a
+ *                 reversed range swapped first (randomR): exactly one `next`;
+ *   kind[l] == 0  the link-table entry as ever (0 µs without a table), the
+ *                 ordinal counting as ever.
+ * Live links never drop; the transmission time (msg_bytes / link_bw) is added
+ * on top, as it is for table entries.  Equal, draw for draw, to the oracle's
+ * live mode.  Per-message delays then cost 8 bytes of HBM per replica instead
+ * of 4 * n_links * link_depth.
+ *
+ * Call after tw_load and before the next tw_reset / tw_run; the arrays are
+ * copied; NULL turns it off (later sends read the table again).  tw_load drops
+ * it.  TW_ERR_STATE before a load.  TW_ERR_INVALID, with the context as it
+ * was: a null array, a kind above 2, lo < 0 or hi > 0x7FFFFFFF (kind 1: lo
+ * alone is read), a range with k * 1000 > 2147483562 (it would need a second
+ * draw; tw_draw_link_table's bound) -- and a tw_lp_load or tw_lpb_load
+ * context: those run a replica's nodes in parallel, so "the replica's
+ * execution order", which decides who draws what, is not defined there. */
+typedef struct tw_live_delays {
+    const uint32_t* kind;   /* [n_links] 0 table, 1 constant lo, 2 U[lo,hi] */
+    const int64_t*  lo;     /* [n_links] */
+    const int64_t*  hi;     /* [n_links] */
+    int64_t seed_base;      /* replica r draws from mkStdGen(seed_base + r) */
+} tw_live_delays;
+int tw_set_live_delays(tw_ctx* ctx, const tw_live_delays* spec);
+/* Generator steps of the whole batch since the last tw_reset (or
+ * tw_set_live_delays): the kind-2 sends.  0 while live delays are off.  Blocks
+ * until the last run has finished.  TW_ERR_STATE before a load. */
+int tw_live_stats(tw_ctx* ctx, uint64_t* draws);
+
 /* ------------------------------------------------- node-partitioned (LP) mode
  * One huge scenario (n_replicas = 1) split by node across contexts / GPUs
  * (BASELINE config 4).  Each lane runs one node as a logical process with its

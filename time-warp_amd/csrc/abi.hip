@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/timewarp.h"
+#include "live_plan.hpp"
 #include "lp_trace_plan.hpp"
 #include "measure_combine.hpp"
 #include "shard.hpp"
@@ -605,6 +606,43 @@ int tw_read_final(tw_ctx* c, int64_t* max_final_t, uint64_t* delivered, uint64_t
     if (delivered) *delivered = dl;
     if (dropped) *dropped = dr;
     if (events) *events = ev;
+    return TW_OK;
+}
+
+// Live delays: the checks and the per-link descriptors are made once
+// (live_plan.hpp) and handed to every shard, whose first replica's seed is
+// seed_base + its first replica's index in the batch.  Nothing changes unless
+// every check passes.
+int tw_set_live_delays(tw_ctx* c, const tw_live_delays* spec) {
+    if (!c || c->sh.empty()) return TW_ERR_INVALID;
+    for (tw_shard* s : c->sh)
+        if (!sh_loaded(s)) return TW_ERR_STATE;
+    for (tw_shard* s : c->sh)
+        if (sh_is_lp(s)) return TW_ERR_INVALID;  // tw_lp_load, tw_lpb_load: no replica execution order
+    std::vector<LiveLink> desc;
+    if (spec) {
+        int rc = live_plan(spec, sh_links(c->sh[0]), desc);
+        if (rc) return rc;
+        if (desc.empty()) desc.resize(1);  // (a scenario without links: a non-null table all the same)
+    }
+    for (size_t i = 0; i < c->sh.size(); ++i) {
+        const uint32_t b0 = i < c->rep0.size() ? c->rep0[i] : 0u;
+        int rc = sh_set_live(c->sh[i], spec ? desc.data() : nullptr, spec ? spec->seed_base + (int64_t)b0 : 0);
+        if (rc) return rc;
+    }
+    return TW_OK;
+}
+
+int tw_live_stats(tw_ctx* c, uint64_t* draws) {
+    if (!c || !draws) return TW_ERR_INVALID;
+    uint64_t n = 0;
+    for (tw_shard* s : c->sh) {
+        uint64_t k = 0;
+        int rc = sh_live_stats(s, &k);
+        if (rc) return rc;
+        n += k;
+    }
+    *draws = n;
     return TW_OK;
 }
 

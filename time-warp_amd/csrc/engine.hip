@@ -45,6 +45,7 @@
 #include "shard.hpp"
 #include "run_state.hpp"
 #include "load_plan.hpp"
+#include "live_plan.hpp"
 #include "sweep_classify.hpp"
 #include "sweep_dev.hpp"
 #include "prefix_classify.hpp"
@@ -87,6 +88,14 @@ struct tw_shard {
     TickGraph tg;
     Sweep sw;
     Prefix px;
+    // live delays (tw_set_live_delays): the load's buffers behind Dev::live_*
+    // (made at the first call, kept while it is turned off and on again) and
+    // the seed of the shard's first replica
+    uint4* lv_desc = nullptr;
+    uint2* lv_gen = nullptr;
+    uint32_t* lv_n = nullptr;
+    unsigned long long* lv_sum = nullptr;
+    int64_t lv_seed0 = 0;
     Dev dwin() const {                // the descriptor the device loop's kernels get
         Dev x = d;
         x.win = ex.win_buf;
@@ -110,6 +119,7 @@ int dalloc(tw_shard* c, T** p, size_t n) {
 void free_all(tw_shard* c) {
     for (void* p : c->allocs) (void)hipFree(p);
     c->allocs.clear();
+    c->lv_desc = nullptr; c->lv_gen = nullptr; c->lv_n = nullptr; c->lv_sum = nullptr;
     c->px.unload();
     c->sw.unload();
     trace_release(c->d);
@@ -135,9 +145,9 @@ struct Geo {
     static constexpr int WG = WG_, NC = NC_, TPW = TPW_, SPILL = SPILL_;
     static constexpr bool FAR_RUNS = !LP_ && RUNS_;  // (LP lanes and compact replicas: the HBM heap only)
     static constexpr size_t LDS = fixed_lds_bytes<WG_, NC_, LP_, RUNS_>();
-    template <bool GS, bool PRW, bool FIP, bool TR>
+    template <bool GS, bool PRW, bool FIP, bool TR, bool LV = false>
     static RunKernel kernel() {
-        return tw_run_kernel<LP_, WG_, NC_, TPW_, RUNS_, GS, PRW, FIP, TR>;
+        return tw_run_kernel<LP_, WG_, NC_, TPW_, RUNS_, GS, PRW, FIP, TR, LV>;
     }
 };
 using GeoDense = Geo<false, TW_WG, TW_NEAR_CAP, 64, true, true, TW_NEAR_CAP>;
@@ -177,16 +187,23 @@ static bool ordered_ties(const tw_shard* c) {
 //   batched device loop's per-replica windows (prw), TRACE records kept (tr:
 //   tw_set_trace on a batched LP context, tw_lp_set_trace on a node-partitioned
 //   one; the others compile Lane::trace_rec out);
-//   replicas: the fork-in-place variant (ip: Lane::fork_in_place).
+//   replicas: the fork-in-place variant (ip: Lane::fork_in_place), and each of
+//   the two once more with live delays (lv: Lane::live_entry; tw_set_live_delays).
 struct Variant {
-    bool gs, prw, ip, tr;
-    bool operator==(const Variant& o) const { return gs == o.gs && prw == o.prw && ip == o.ip && tr == o.tr; }
+    bool gs, prw, ip, tr, lv = false;
+    bool operator==(const Variant& o) const {
+        return gs == o.gs && prw == o.prw && ip == o.ip && tr == o.tr && lv == o.lv;
+    }
 };
 template <class G, class F>
 static void each_kernel(F&& f) {  // f(RunKernel, Variant)
     constexpr bool T = true, N = false;
     f(G::template kernel<N, N, N, N>(), Variant{N, N, N, N});
     if constexpr (G::IP) f(G::template kernel<N, N, T, N>(), Variant{N, N, T, N});
+    if constexpr (!G::LP) {
+        f(G::template kernel<N, N, N, N, T>(), Variant{N, N, N, N, T});
+        if constexpr (G::IP) f(G::template kernel<N, N, T, N, T>(), Variant{N, N, T, N, T});
+    }
     if constexpr (G::LP) {
         f(G::template kernel<T, N, N, N>(), Variant{T, N, N, N});
         f(G::template kernel<N, T, N, N>(), Variant{N, T, N, N});
@@ -217,7 +234,7 @@ static void launch_run(tw_shard* c, hipStream_t st, int64_t t_end, uint64_t limi
     // grid: workgroups to launch, 0 = one per WG replicas (the prefix pilot
     // launches the first only; replica kernels, whose workgroups serve their own block)
     uint32_t blocks = (grid && !G::LP) ? grid : (uint32_t)((c->d.R + G::WG - 1) / G::WG);
-    Variant v{false, false, use_ip<G>(c), false};
+    Variant v{false, false, use_ip<G>(c), false, c->d.live_desc != nullptr};
     if constexpr (G::LP) {
         v = Variant{blocks > c->lp_grid, c->d.rw && c->d.win, false, c->d.trace_cap != 0};
         if (v.gs) blocks = c->lp_grid;
@@ -661,7 +678,67 @@ int sh_reset(tw_shard* c) {
                        (const int64_t*)c->main_regs, (const int64_t*)c->nv_init, (const uint32_t*)c->listen_init,
                        c->lpm.lp ? 1 : 0, c->seq0, c->tid0);
     HIPCHK(hipGetLastError());
+    if (d.live_gen) {  // every replica's generator back to mkStdGen(seed_base + its index)
+        hipLaunchKernelGGL(tw_live_seed_kernel, dim3(blocks), dim3(TW_WG), 0, st, d, c->lv_seed0);
+        HIPCHK(hipGetLastError());
+    }
     c->px.fresh = true;
+    return TW_OK;
+}
+
+// tw_set_live_delays on one shard: desc = live_plan's descriptors of the
+// loaded scenario's links (null: off), seed0 = the seed of the shard's first
+// replica.  Seeds the generators, as the next sh_reset will again.
+static_assert(sizeof(LiveLink) == sizeof(uint4), "a SEND loads a link's descriptor as one quad");
+int sh_set_live(tw_shard* c, const LiveLink* desc, int64_t seed0) {
+    if (!c) return TW_ERR_INVALID;
+    if (!c->loaded) return TW_ERR_STATE;
+    if (c->lpm.lp) return TW_ERR_INVALID;  // (a replica's nodes run in parallel: no execution order to draw in)
+    HIPCHK(hipSetDevice(c->device));
+    Dev& d = c->d;
+    if (!desc) {
+        d.live_desc = nullptr; d.live_gen = nullptr; d.live_n = nullptr;
+        return TW_OK;
+    }
+    if (!c->lv_desc) {
+        uint4* ld = nullptr;
+        uint2* lg = nullptr;
+        uint32_t* ln = nullptr;
+        unsigned long long* ls = nullptr;
+        Alloc A{c};
+        A(ld, d.L);
+        A(lg, d.R);
+        A(ln, d.R);
+        A(ls, 1);
+        if (A.rc) return A.rc;  // (what was allocated goes with the load)
+        c->lv_desc = ld; c->lv_gen = lg; c->lv_n = ln; c->lv_sum = ls;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));  // (a run in flight reads the descriptors)
+    if (d.L) HIPCHK(hipMemcpy(c->lv_desc, desc, 16ull * d.L, hipMemcpyHostToDevice));
+    d.live_desc = c->lv_desc; d.live_gen = c->lv_gen; d.live_n = c->lv_n;
+    c->lv_seed0 = seed0;
+    hipLaunchKernelGGL(tw_live_seed_kernel, dim3((uint32_t)((d.R + TW_WG - 1) / TW_WG)), dim3(TW_WG), 0, c->stream, d,
+                       seed0);
+    HIPCHK(hipGetLastError());
+    return TW_OK;
+}
+
+// the shard's generator steps since the last reset (0: live delays off)
+int sh_live_stats(tw_shard* c, uint64_t* draws) {
+    if (!c || !draws) return TW_ERR_INVALID;
+    if (!c->loaded) return TW_ERR_STATE;
+    *draws = 0;
+    const Dev& d = c->d;
+    if (!d.live_n) return TW_OK;
+    HIPCHK(hipSetDevice(c->device));
+    unsigned long long h = 0;
+    HIPCHK(hipMemsetAsync(c->lv_sum, 0, 8, c->stream));
+    hipLaunchKernelGGL(tw_live_sum_kernel, dim3((uint32_t)((d.R + TW_WG - 1) / TW_WG)), dim3(TW_WG), 0, c->stream, d,
+                       c->lv_sum);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&h, c->lv_sum, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *draws = h;
     return TW_OK;
 }
 
@@ -1786,6 +1863,8 @@ int sh_prof_read(tw_shard* c, unsigned long long* out, size_t cap, int reset) {
 uint32_t sh_replicas(tw_shard* c) { return c->lpm.lpb ? c->lpm.n_rep : c->d.R; }
 uint32_t sh_nodes(tw_shard* c) { return c->lpm.lpb ? c->d.Ntot : c->d.N; }
 bool sh_is_lp(tw_shard* c) { return c->lpm.lp; }
+bool sh_loaded(tw_shard* c) { return c->loaded; }
+uint32_t sh_links(tw_shard* c) { return c->d.L; }
 int sh_device(tw_shard* c) { return c->device; }
 
 int sh_set_trace(tw_shard* c, uint32_t cap) {

@@ -3,6 +3,8 @@
 // the window-loop kernels.  Included by engine.hip.
 #pragma once
 #include "tw_dev.hpp"
+#include "stdgen_dev.hpp"
+#include "live_plan.hpp"
 
 #define TW_NEAR_CAP 16          // on-chip queue entries per replica (LDS)
 #define TW_WG 256               // lanes per workgroup (4 waves share one program image)
@@ -293,7 +295,10 @@ struct BoolC {
 // launches under the tie orders where a forked child is always the next pop
 // TR (LP only): TRACE records are kept (trace_rec) -- the variant the host
 // launches for a batched LP context while tw_set_trace is on
-template <bool LP, int WG, int NC, bool RUNS = true, bool IP = false, bool TR = false>
+// LV (replicas only): live delays (live_entry) -- the variant the host launches
+// while tw_set_live_delays is on; the others compile it out, so a context
+// without live delays runs the code it ran before there were any
+template <bool LP, int WG, int NC, bool RUNS = true, bool IP = false, bool TR = false, bool LV = false>
 struct Lane {
     // the replica kernels keep monotone far runs (LDS bookkeeping + HBM FIFOs)
     // unless built without them (the compact geometry: far events go to the
@@ -415,6 +420,21 @@ struct Lane {
 
     __device__ __forceinline__ void fail(uint32_t st) {
         if (status == TW_REP_RUNNING) status = st;
+    }
+    // LV: a send's link entry under live delays (tw_set_live_delays; the
+    // oracle's link_entry).  lv = the link's descriptor, gs / gn = the replica's
+    // generator and step count as loaded beside it, e_tab = the table's entry.
+    // Only a lane that draws stores: the generator moves at a kind-2 send and
+    // nowhere else.  Live links never drop (bit 31 stays clear: lo + k - 1 <=
+    // 0x7FFFFFFF, live_plan)
+    __device__ __forceinline__ uint32_t live_entry(uint4 lv, uint2 gs, uint32_t gn, uint32_t e_tab) {
+        if (lv.x == 0) return e_tab;
+        if (lv.x == 1) return lv.y;
+        Gen g{(int32_t)gs.x, (int32_t)gs.y};
+        const uint32_t z = next(g);
+        gp(c.live_gen)[r] = make_uint2((uint32_t)g.s1, (uint32_t)g.s2);
+        gp(c.live_n)[r] = gn + 1u;
+        return lv.y + live_mod(z - 1u, lv.z, lv.w);
     }
     // The running thread's registers r0..r3: the LDS register file (the
     // interpreter's operand indices are per lane)
@@ -1811,13 +1831,24 @@ struct Lane {
                     // (a one-deep table -- one delay per link, every scenario but
                     // record-replay -- needs no ordinal: its entry is known now)
                     uint32_t ord = 0;
+                    // LV: the link's live descriptor, the replica's generator and
+                    // its step count join them
+                    [[maybe_unused]] uint4 lv = make_uint4(0u, 0u, 0u, 0u);
+                    [[maybe_unused]] uint2 gs = make_uint2(0u, 0u);
+                    [[maybe_unused]] uint32_t gn = 0;
+                    if constexpr (LV) {
+                        lv = gp(c.live_desc)[link];
+                        gs = gp(c.live_gen)[r];
+                        gn = gp(c.live_n)[r];
+                    }
                     if (c.D > 1) {
                         ord = gp(c.link_ord)[lix(link)];
                         gp(c.link_ord)[lix(link)] = ord + 1;
                     }
                     uint4 dh = make_uint4(0x80000000u, 0, 0, 0);
                     if (LP) dh = gp(c.link_dsth)[link];  // destination | heavy, its inbox
-                    const uint32_t e = c.link_table ? gp(c.link_table)[tix(link, ord)] : 0u;
+                    uint32_t e = c.link_table ? gp(c.link_table)[tix(link, ord)] : 0u;
+                    if constexpr (LV) e = live_entry(lv, gs, gn, e);
                     if (e & TW_LINK_DROP) {
                         cinc(CW_DR);
                         hash(th.w1, TW_KIND_DROP | kind, payload);
@@ -2513,6 +2544,31 @@ __global__ void __launch_bounds__(TW_WG) tw_init_kernel(Dev c, uint32_t main_pc,
         for (uint32_t n = 0; n < c.N; ++n) gp(c.bind)[(size_t)n * c.R + r] = listen_init[n];
 }
 
+// Live delays: replica r's generator is mkStdGen(seed0 + r), seed0 = the
+// context's seed_base + the shard's first replica (tw_reset, tw_set_live_delays)
+__global__ void __launch_bounds__(TW_WG) tw_live_seed_kernel(Dev c, int64_t seed0) {
+    const uint32_t r = blockIdx.x * TW_WG + threadIdx.x;
+    if (r >= c.R) return;
+    const Gen g = mk_stdgen(seed0 + (int64_t)r);
+    gp(c.live_gen)[r] = make_uint2((uint32_t)g.s1, (uint32_t)g.s2);
+    gp(c.live_n)[r] = 0u;
+}
+
+// tw_live_stats: the batch's generator steps, one atomic per workgroup
+__global__ void __launch_bounds__(TW_WG) tw_live_sum_kernel(Dev c, unsigned long long* out) {
+    __shared__ unsigned long long part[TW_WG / 64];
+    const uint32_t r = blockIdx.x * TW_WG + threadIdx.x;
+    unsigned long long v = r < c.R ? gp(c.live_n)[r] : 0u;
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t = 0;
+        for (int i = 0; i < TW_WG / 64; ++i) t += part[i];
+        if (t) atomicAdd(out, t);
+    }
+}
+
 // LDS per workgroup: near heap keys + slots, the running threads' register
 // files, the cold words, then the program image and constant pool, so
 // instruction fetch and time constants never leave the CU.
@@ -2530,14 +2586,16 @@ __host__ __device__ constexpr size_t fixed_lds_bytes() {
 // LP lanes' prologue: the near spill's entries and the far heap's top loaded
 // together (round 6: C5 1,366 -> 1,341 ms, C4 flat)
 // TR: the LP kernel that keeps TRACE records (Lane::trace_rec)
+// LV: the replica kernel of a context with live delays (Lane::live_entry)
 template <bool LP, int WG, int NC, int TPW = 64, bool RUNS = true, bool GS = false, bool PRW = false, bool IP = false,
-          bool TR = false>
+          bool TR = false, bool LV = false>
 __global__ void __launch_bounds__(WG * 64 / TPW)
     __attribute__((amdgpu_waves_per_eu(LP ? TW_LP_WAVES : !RUNS ? 2 : (WG * 64 / TPW + 255) / 256,
                                        LP ? TW_LP_WAVES : 2)))
 tw_run_kernel(Dev c, int64_t t_end, uint64_t max_events, uint32_t budget) {
     constexpr bool HR = !LP && RUNS;
     static_assert(LP || !TR, "TRACE-recording instantiations are LP kernels");
+    static_assert(!LP || !LV, "live delays are drawn in a replica's execution order: replica kernels only");
     // device-driven windows: the window, its work list and whether this is the
     // window's first tick (the only one that drains inboxes) come from the device
     bool fresh = true;
@@ -2674,7 +2732,7 @@ tw_run_kernel(Dev c, int64_t t_end, uint64_t max_events, uint32_t budget) {
                     break;  // (the next block of the work list)
             }
 
-            Lane<LP, WG, NC, RUNS, IP, TR> L;
+            Lane<LP, WG, NC, RUNS, IP, TR, LV> L;
             L.c = c;
             L.r = r;
             L.nk = s_k + li;
@@ -3062,7 +3120,7 @@ tw_run_kernel(Dev c, int64_t t_end, uint64_t max_events, uint32_t budget) {
                 const uint4 ix4 = *L.rqp(RQ_IDX);
         #pragma unroll
                 for (int j = 0; j < TW_RUNS; ++j) {
-                    sc[(SC_RH0 + j) * SR] = Lane<LP, WG, NC, RUNS, IP, TR>::q_at(ix4, j);
+                    sc[(SC_RH0 + j) * SR] = Lane<LP, WG, NC, RUNS, IP, TR, LV>::q_at(ix4, j);
                     sc[(SC_RC0 + j) * SR] = L.rqp(RQ_TAIL + j)->w;
                 }
             }

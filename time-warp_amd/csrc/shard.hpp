@@ -46,6 +46,13 @@ TW_HIDDEN int sh_prefix_stats(tw_shard* c, int64_t* t0, uint64_t* events, uint64
 // whether that run verified, the testing hook's mismatch count
 TW_HIDDEN int sh_prefix_clean_stats(tw_shard* c, uint32_t* claimed, uint64_t* rows_skipped, uint64_t* bytes_stored,
                                     uint32_t* verified, uint64_t* audit);
+// live delays (tw_set_live_delays): desc = live_plan.hpp's descriptors of the
+// loaded links (null: off), seed0 = the seed of the shard's first replica;
+// TW_ERR_INVALID for a node-partitioned or batched LP shard.  sh_live_stats:
+// the shard's generator steps since the last reset
+struct LiveLink;
+TW_HIDDEN int sh_set_live(tw_shard* c, const LiveLink* desc, int64_t seed0);
+TW_HIDDEN int sh_live_stats(tw_shard* c, uint64_t* draws);
 TW_HIDDEN int sh_set_trace(tw_shard* c, uint32_t cap);
 // batched LP, tracing on: tw_lp_batch<true> runs the due runs' batchable prefixes
 // and records their TRACEs (off: they stay on the chain); from the next sh_reset
@@ -95,6 +102,8 @@ TW_HIDDEN int sh_prof_read(tw_shard* c, unsigned long long* out, size_t cap, int
 TW_HIDDEN uint32_t sh_replicas(tw_shard* c);
 TW_HIDDEN uint32_t sh_nodes(tw_shard* c);
 TW_HIDDEN bool sh_is_lp(tw_shard* c);
+TW_HIDDEN bool sh_loaded(tw_shard* c);
+TW_HIDDEN uint32_t sh_links(tw_shard* c);  // links of the loaded scenario
 TW_HIDDEN int sh_device(tw_shard* c);
 
 // node-partitioned (LP) mode

@@ -215,6 +215,14 @@ struct Dev {
     // batched LP with tw_set_trace on: TRACE records emitted per replica, [2^rep_lg] (a replica
     // context counts in SC_TRACE_N); every record claims its index here (Lane::trace_rec)
     uint64_t* trace_n;
+    // live delays (tw_set_live_delays; replica contexts, the LV kernels): a SEND
+    // over a link whose descriptor's kind is not 0 takes its delay from the
+    // descriptor and the replica's StdGen instead of the link table.  All null
+    // while live delays are off.  The generator is the replica's own: the
+    // prefix snapshot (prefix.hip) and the sweeps never touch it
+    const uint4* live_desc;  // [L] live_plan.hpp's LiveLink {kind, lo, k, reciprocal}
+    uint2* live_gen;         // [R] the replica's StdGen {s1, s2}
+    uint32_t* live_n;        // [R] its steps since the last reset (tw_live_stats)
 };
 // index of scalar field f of lane / replica r
 __host__ __device__ __forceinline__ size_t sc_ix(const Dev& c, uint32_t f, size_t r) {

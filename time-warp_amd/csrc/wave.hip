@@ -29,6 +29,8 @@
 #include <cstdlib>
 
 #include "tw_dev.hpp"
+#include "stdgen_dev.hpp"
+#include "live_plan.hpp"
 
 #define TW_STEP_CAP (1u << 22)  // instructions per thread step (== oracle kStepCap, engine.hip)
 
@@ -165,7 +167,10 @@ __device__ __forceinline__ int64_t tx_us_w(const Dev CAS* dv, uint64_t link, uin
 }
 
 // One replica on one wavefront.  K = near-queue entries per lane (64*K total).
-template <int K>
+// LV: live delays (tw_set_live_delays) -- a SEND may take its delay from the
+// link's descriptor and the replica's StdGen; compiled out of the kernels a
+// context without live delays runs.
+template <int K, bool LV = false>
 struct Wave {
     const Dev CAS* dv;  // the device context, read through the scalar cache on use
     uint32_t r;      // replica
@@ -854,7 +859,26 @@ struct Wave {
                 uint32_t GAS* op_ = gp(dv->link_ord) + ix(link);
                 const uint32_t ord = rfl(*op_);
                 st32(op_, ord + 1);
-                const uint32_t e = dv->link_table ? rfl(gp(dv->link_table)[ix((size_t)link * dv->D + ord % dv->D)]) : 0u;
+                uint32_t e = dv->link_table ? rfl(gp(dv->link_table)[ix((size_t)link * dv->D + ord % dv->D)]) : 0u;
+                if constexpr (LV) {
+                    // the oracle's link_entry: kind 1 the constant, kind 2 one step of the
+                    // replica's generator; the descriptor (a scalar load) and the
+                    // generator's words are in flight together
+                    const uint4 lv = cp(dv->live_desc)[link];
+                    uint32_t GAS* gw = (uint32_t GAS*)(gp(dv->live_gen) + r);
+                    uint32_t GAS* gc = gp(dv->live_n) + r;
+                    const uint32_t s1 = rfl(gw[0]), s2 = rfl(gw[1]), gn = rfl(*gc);
+                    if (lv.x == 1) {
+                        e = lv.y;
+                    } else if (lv.x == 2) {
+                        Gen g{(int32_t)s1, (int32_t)s2};
+                        const uint32_t z = next(g);
+                        st32(gw, (uint32_t)g.s1);
+                        st32(gw + 1, (uint32_t)g.s2);
+                        st32(gc, gn + 1u);
+                        e = lv.y + live_mod(z - 1u, lv.z, lv.w);
+                    }
+                }
                 if (e & TW_LINK_DROP) {
                     cw->dr = rfl(cw->dr) + 1;
                     hash_add(th.w1, term(now, TW_KIND_DROP | kind, payload));
@@ -987,7 +1011,7 @@ struct Wave {
     }
 };
 
-template <int K>
+template <int K, bool LV = false>
 __global__ void __launch_bounds__(64) tw_wave_kernel(const Dev* dptr, int64_t t_end, uint64_t max_events,
                                                       uint32_t budget) {
     const Dev CAS* dv = cp(dptr);
@@ -997,7 +1021,7 @@ __global__ void __launch_bounds__(64) tw_wave_kernel(const Dev* dptr, int64_t t_
     const size_t R = dv->R;
     const uint32_t status0 = (uint32_t)rfl64(sc[SC_STATUS * R]);
     if (status0 != TW_REP_RUNNING) return;
-    Wave<K> W(dv, r);
+    Wave<K, LV> W(dv, r);
     W.status = status0;
     W.now = rfl64s((int64_t)sc[SC_NOW * R]);
     W.final_t = rfl64s((int64_t)sc[SC_FINAL_T * R]);
@@ -1245,14 +1269,14 @@ hipError_t wave_launch(const Dev& d, const Dev* d_dev, hipStream_t st, int64_t t
     // not from kernel arguments held in scalar registers for the whole launch
     hipError_t e = hipMemcpyAsync((void*)d_dev, &d, sizeof(Dev), hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return e;
-    if (d.wave_k == 32)
-        hipLaunchKernelGGL((tw_wave_kernel<32>), dim3(d.R), dim3(64), 0, st, d_dev, t_end, limit, budget);
-    else if (d.wave_k == 24)
-        hipLaunchKernelGGL((tw_wave_kernel<24>), dim3(d.R), dim3(64), 0, st, d_dev, t_end, limit, budget);
-    else if (d.wave_k == 4)
-        hipLaunchKernelGGL((tw_wave_kernel<4>), dim3(d.R), dim3(64), 0, st, d_dev, t_end, limit, budget);
-    else
-        return hipErrorInvalidValue;
+    // (a context with live delays, Dev::live_desc, runs the LV instantiation)
+    void (*k)(const Dev*, int64_t, uint64_t, uint32_t) = nullptr;
+    const bool lv = d.live_desc != nullptr;
+    if (d.wave_k == 32) k = lv ? tw_wave_kernel<32, true> : tw_wave_kernel<32>;
+    else if (d.wave_k == 24) k = lv ? tw_wave_kernel<24, true> : tw_wave_kernel<24>;
+    else if (d.wave_k == 4) k = lv ? tw_wave_kernel<4, true> : tw_wave_kernel<4>;
+    else return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k, dim3(d.R), dim3(64), 0, st, d_dev, t_end, limit, budget);
     return hipGetLastError();
 }
 

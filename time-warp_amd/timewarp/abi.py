@@ -98,6 +98,16 @@ class TwTableDraw(C.Structure):
     ]
 
 
+class TwLiveDelays(C.Structure):
+    """tw_live_delays: per-link kind / lo / hi and the batch's seed base."""
+    _fields_ = [
+        ("kind", C.c_void_p),
+        ("lo", C.c_void_p),
+        ("hi", C.c_void_p),
+        ("seed_base", C.c_int64),
+    ]
+
+
 class TwMeasureSpec(C.Structure):
     """tw_measure_spec: the two TRACE tags to join and the histogram's shape."""
     _fields_ = [

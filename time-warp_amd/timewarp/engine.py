@@ -16,7 +16,7 @@ from typing import Optional
 
 import numpy as np
 
-from .abi import (MEASURE_DTYPE, RESULT_DTYPE, TwLpState, TwMeasureOut, TwMeasureSpec, TwStats,
+from .abi import (MEASURE_DTYPE, RESULT_DTYPE, TwLiveDelays, TwLpState, TwMeasureOut, TwMeasureSpec, TwStats,
                   TwTableDraw)
 from .scenario import Scenario
 
@@ -33,7 +33,8 @@ EXPORTS = ["tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_ru
            "tw_lp_tick_end", "tw_lp_progress", "tw_lp_run_windows", "tw_lpb_load", "tw_lpb_windows",
            "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms", "tw_set_sweep", "tw_sweep_stats",
            "tw_set_prefix", "tw_prefix_stats", "tw_set_measure_keys", "tw_measure_phases_ms",
-           "tw_prefix_clean_stats", "tw_set_trace_batch", "tw_lp_set_trace", "tw_lp_read_trace", "tw_lp_measure"]
+           "tw_prefix_clean_stats", "tw_set_trace_batch", "tw_lp_set_trace", "tw_lp_read_trace", "tw_lp_measure",
+           "tw_set_live_delays", "tw_live_stats"]
 GEOMETRIES = ("dense", "sparse", "half", "wave", "lp", "narrow", "lpb", "compact")  # TW_GEO_* order
 
 # tw_trace_rec (include/timewarp.h)
@@ -132,6 +133,10 @@ def load_library(path: Optional[str] = None):
         lib.tw_lp_measure.argtypes = [C.c_void_p, C.POINTER(TwMeasureSpec), C.POINTER(TwMeasureOut), C.c_void_p]
         for name in ("tw_lp_set_trace", "tw_lp_read_trace", "tw_lp_measure"):
             getattr(lib, name).restype = C.c_int
+    if hasattr(lib, "tw_set_live_delays"):  # (an older in-tree build under TW_LIB lacks them)
+        lib.tw_set_live_delays.argtypes = [C.c_void_p, C.POINTER(TwLiveDelays)]
+        lib.tw_live_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.tw_set_live_delays.restype = lib.tw_live_stats.restype = C.c_int
     for name in ("tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_run", "tw_set_tie_mode", "tw_load", "tw_reset", "tw_run", "tw_read_results", "tw_read_hashes", "tw_read_final",
                  "tw_last_launch_ms", "tw_lp_load", "tw_lp_window", "tw_lp_take_outbox", "tw_lp_inject",
                  "tw_lp_results", "tw_set_trace", "tw_read_trace", "tw_tie_audit", "tw_set_counter_base",
@@ -403,6 +408,46 @@ class Engine:
         return {"claimed_slots": int(cl.value), "rows_skipped": int(rows.value), "bytes_stored": int(by.value),
                 "verified": bool(ver.value), "audit_mismatches": int(bad.value)}
 
+    def set_live_delays(self, scn_or_arrays, seed_base: int = 0) -> "Engine":
+        """Live delays (tw_set_live_delays): from now on a send over link l
+        takes its delay from (kind, lo, hi)[l] and the replica's own StdGen,
+        mkStdGen(seed_base + replica), stepped in the replica's execution
+        order -- kind 1: lo; kind 2: one randomR(lo, hi) draw; kind 0: the link
+        table as ever.  `scn_or_arrays` is a Scenario (its live_kind / live_lo
+        / live_hi), a (kind, lo, hi) triple, or None: off.  Call after load
+        and before the next reset / run; every reset re-seeds, a run continued
+        after a cut keeps drawing where it stopped.  ERR_STATE before a load,
+        ERR_INVALID for a bad spec and for "lpb" and node-partitioned contexts
+        (a replica's nodes run in parallel there: no order to draw in)."""
+        if scn_or_arrays is None:
+            _check(self.lib.tw_set_live_delays(self.ctx, None), "tw_set_live_delays")
+            return self
+        if isinstance(scn_or_arrays, Scenario):
+            arrs = (scn_or_arrays.live_kind, scn_or_arrays.live_lo, scn_or_arrays.live_hi)
+            if any(a is None for a in arrs):
+                raise ValueError("set_live_delays: the scenario has no live_kind / live_lo / live_hi")
+        else:
+            arrs = tuple(scn_or_arrays)
+            if len(arrs) != 3:
+                raise ValueError("set_live_delays: a Scenario, a (kind, lo, hi) triple or None")
+        kind = np.ascontiguousarray(arrs[0], dtype=np.uint32)
+        lo = np.ascontiguousarray(arrs[1], dtype=np.int64)
+        hi = np.ascontiguousarray(arrs[2], dtype=np.int64)
+        if self.scn is not None:
+            L = self.scn.topo.n_links
+            if kind.shape != (L,) or lo.shape != (L,) or hi.shape != (L,):
+                raise ValueError("set_live_delays: kind, lo and hi need one entry per link")
+        spec = TwLiveDelays(kind=kind.ctypes.data, lo=lo.ctypes.data, hi=hi.ctypes.data, seed_base=int(seed_base))
+        _check(self.lib.tw_set_live_delays(self.ctx, C.byref(spec)), "tw_set_live_delays")
+        return self
+
+    def live_stats(self) -> int:
+        """Generator steps of the whole batch since the last reset: its kind-2
+        sends (tw_live_stats; 0 while live delays are off)."""
+        n = C.c_uint64(0)
+        _check(self.lib.tw_live_stats(self.ctx, C.byref(n)), "tw_live_stats")
+        return int(n.value)
+
     def set_counter_base(self, seq0: int, tid0: int = 1) -> "Engine":
         """Testing hook: start the 32-bit insertion / thread counters at these
         values from the next reset on (TW_REP_ERR_COUNTER guard)."""
@@ -561,10 +606,14 @@ def lpb_short_link_destinations(scn: Scenario, lookahead_us: int) -> np.ndarray:
 
 
 def run_scenario(scn: Scenario, device: int = 0, t_end: int = T_INF, max_events: int = UNLIMITED,
-                 geometry: Optional[str] = None):
-    """Load + run to quiescence; returns (stats, results, hashes)."""
+                 geometry: Optional[str] = None, live_seed_base: Optional[int] = None):
+    """Load + run to quiescence; returns (stats, results, hashes).  With
+    `live_seed_base`, the scenario's live delays are drawn at each send from
+    replica r's mkStdGen(live_seed_base + r) (Engine.set_live_delays)."""
     with Engine(device) as e:
         e.load(scn, geometry=geometry)
+        if live_seed_base is not None:
+            e.set_live_delays(scn, seed_base=live_seed_base)
         st = e.run(t_end, max_events)
         return st, e.results(), e.hashes()
 

@@ -73,7 +73,8 @@ class Scenario:
     msg_bytes: Optional[np.ndarray] = None    # uint32 [n_msg_kinds]: BinaryP wire size per kind
     link_bw: Optional[np.ndarray] = None      # uint64 [n_links]: bytes/s (0 = no transmission time)
     meta: dict = field(default_factory=dict)
-    # oracle-only: the reference's live Delays function (kind/lo/hi per link)
+    # the reference's live Delays function (kind / lo / hi per link): what
+    # Engine.set_live_delays and the oracle's live mode draw from at each send
     live_kind: Optional[np.ndarray] = None
     live_lo: Optional[np.ndarray] = None
     live_hi: Optional[np.ndarray] = None

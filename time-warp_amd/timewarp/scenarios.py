@@ -71,7 +71,7 @@ def draw_table(n_links: int, n_replicas: int, drawn_links, lo, hi, link_depth: i
 def token_ring(n_nodes: int = 16, n_replicas: int = 1, launch_duration: int = sec(20),
                token_passing_delay: int = sec(3), allowed_progress_delay: int = sec(5),
                network_delay=(ms(1), ms(5)), drop_log2: int = 0, seed_base: int = 0,
-               link_depth: int = 1, near_horizon_us: int = sec(10), drawer=None) -> Scenario:
+               link_depth: int = 1, near_horizon_us: int = sec(10), drawer=None, live: bool = False) -> Scenario:
     """examples/token-ring/Main.hs lowered.
 
     Node ids: ring nodes 0..N-1 are the reference's ``no = 1..N``
@@ -80,6 +80,10 @@ def token_ring(n_nodes: int = 16, n_replicas: int = 1, launch_duration: int = se
     observer].  ``call`` (MonadRpc, absent) is lowered to a one-way send.
     Delays (:73-77): observer links ConnectedIn 0; ring links U[1 ms, 5 ms];
     optional drop with probability 2^-drop_log2 per send (config 3 nastiness).
+    ``live=True`` draws no table (``link_table`` stays None): the delays are
+    meant to be drawn at each send, from ``live_kind`` / ``live_lo`` /
+    ``live_hi`` (Engine.set_live_delays, run_scenario(live_seed_base=)), as
+    the reference's ``Delays`` function does; live links never drop.
     """
     N = int(n_nodes)
     OBS, SYS = N, N + 1
@@ -175,8 +179,8 @@ def token_ring(n_nodes: int = 16, n_replicas: int = 1, launch_duration: int = se
     live_kind[ring_links] = 2
     live_kind[ring_links + 1] = 1
     live_lo, live_hi = lo.copy(), hi.copy()
-    table = draw_table(L, n_replicas, ring_links, lo, hi, link_depth=link_depth, drop_log2=drop_log2,
-                       seed_base=seed_base, drawer=drawer)
+    table = None if live else draw_table(L, n_replicas, ring_links, lo, hi, link_depth=link_depth,
+                                         drop_log2=drop_log2, seed_base=seed_base, drawer=drawer)
 
     hops = launch_duration // max(1, token_passing_delay) + 2
     max_slots = 3 * N + 64
@@ -259,6 +263,9 @@ def ping_pong(n_replicas: int = 1, round_trips: int = 1, network_delay=(ms(1), m
         main_pc=img.pc_of("main"), main_node=2, link_table=table,
         max_slots=16, queue_capacity=64, near_horizon_us=near_horizon_us,
         meta=dict(config="ping_pong", round_trips=round_trips, seed_base=seed_base),
+        # live delays (Engine.set_live_delays): both links draw U[network_delay] per message
+        live_kind=np.full(2, 2, np.uint32), live_lo=np.full(2, network_delay[0], np.int64),
+        live_hi=np.full(2, network_delay[1], np.int64),
     )
 
 
@@ -358,10 +365,16 @@ def hotspot(n_senders: int = 256, n_replicas: int = 1, msg_num: int = 1000, msg_
     topo = Topology.from_out_lists(S + 2, out)
     table = draw_table(topo.n_links, n_replicas, np.arange(topo.n_links), *network_delay, seed_base=seed_base,
                        drop_log2=drop_log2, drawer=drawer)
+    # live delays (Engine.set_live_delays): every link draws U[network_delay] per message
+    live_lo = np.full(topo.n_links, network_delay[0], np.int64)
+    live_hi = np.full(topo.n_links, network_delay[1], np.int64)
     if bandwidth_bytes_per_s > 0:
         from .wire import bench_message_size, transmission_us
         table[:S] += transmission_us(bench_message_size("Ping", payload_bytes), bandwidth_bytes_per_s)
         table[S:2 * S] += transmission_us(bench_message_size("Pong", payload_bytes), bandwidth_bytes_per_s)
+        for a in (live_lo, live_hi):  # (the transmission time shifts the range as it shifts the table)
+            a[:S] += transmission_us(bench_message_size("Ping", payload_bytes), bandwidth_bytes_per_s)
+            a[S:2 * S] += transmission_us(bench_message_size("Pong", payload_bytes), bandwidth_bytes_per_s)
     max_delay = int(table.max()) if table.size else int(network_delay[1])
     in_flight = (max_delay // max(1, send_delay) + 2) * 2
     max_slots = S * (in_flight + 2) + 64
@@ -379,6 +392,7 @@ def hotspot(n_senders: int = 256, n_replicas: int = 1, msg_num: int = 1000, msg_
                                         np.uint32),
                   lp_max_slots=64, lp_queue_capacity=128,
                   lp_outbox_cap=min(1 << 27, (8 * S + 2 * (S + 1) + 64) * n_replicas)),
+        live_kind=np.full(topo.n_links, 2, np.uint32), live_lo=live_lo, live_hi=live_hi,
     )
 
 
