@@ -550,6 +550,17 @@ int tw_set_sweep(tw_ctx* ctx, int on);
  * victims retired by sweeps, and replicas that had events at a sweep time but
  * were refused (they took the sequential path).  Any pointer may be NULL. */
 int tw_sweep_stats(tw_ctx* ctx, uint64_t* killers, uint64_t* victims, uint64_t* refused_replicas);
+/* How the last tw_run's sweeps applied their kill wakes, summed over the
+ * context's devices (read-only): replicas the sweep ended and therefore swept
+ * on its terminal path (no record or free-stack stores: nothing reads them
+ * before the next tw_reset); kill wakes of such replicas whose effects came
+ * from the table built with the prefix's snapshot, no thread header loaded
+ * (fast), and all other kill wakes, whose headers were loaded (slow: every
+ * kill wake of a replica not on the terminal path, and those of a terminal
+ * replica whose threads no longer match the snapshot).  fast + slow =
+ * tw_sweep_stats' killers.  Results do not
+ * depend on the path.  Any pointer may be NULL. */
+int tw_sweep_path_stats(tw_ctx* ctx, uint64_t* terminal_replicas, uint64_t* fast_entries, uint64_t* slow_entries);
 
 /* The send-free prefix (replica geometries DENSE, NARROW and HALF under
  * TW_TIE_FIFO / TW_TIE_FORKFIRST, tracing off, a scenario without main_regs).

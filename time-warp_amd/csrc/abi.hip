@@ -798,6 +798,21 @@ int tw_sweep_stats(tw_ctx* c, uint64_t* killers, uint64_t* victims, uint64_t* re
     return TW_OK;
 }
 
+int tw_sweep_path_stats(tw_ctx* c, uint64_t* terminal_replicas, uint64_t* fast_entries, uint64_t* slow_entries) {
+    if (!c) return TW_ERR_INVALID;
+    uint64_t k = 0, v = 0, f = 0;
+    for (tw_shard* s : c->sh) {
+        uint64_t a = 0, b = 0, d = 0;
+        int rc = sh_sweep_path_stats(s, &a, &b, &d);
+        if (rc) return rc;
+        k += a; v += b; f += d;
+    }
+    if (terminal_replicas) *terminal_replicas = k;
+    if (fast_entries) *fast_entries = v;
+    if (slow_entries) *slow_entries = f;
+    return TW_OK;
+}
+
 int tw_geometry(tw_ctx* c) {
     if (!c) return TW_ERR_INVALID;
     return sh_geometry(c->sh[0]);

@@ -270,6 +270,12 @@ int sh_create(int device, tw_shard** out) {
     // testing hook: TW_TEST_PREFIX_AUDIT=1 follows every apply that may skip
     // rows with a read-only kernel over the skipped rows (tw_prefix_clean_stats)
     if (const char* a = getenv("TW_TEST_PREFIX_AUDIT")) c->px.audit = atoi(a) != 0;
+    // testing hook: TW_TEST_SWEEP_SLOW=1 keeps every replica on tw_sweep_apply's
+    // general path (no clean bits, no terminal path: the A/B arm of §3t)
+    if (const char* a = getenv("TW_TEST_SWEEP_SLOW")) c->sw.slow = atoi(a) != 0;
+    // ... and TW_TEST_SWEEP_FRAMES=1 keeps tw_sweep_validate's load of every
+    // victim's frames quad (the kill table then carries no verdict bits)
+    if (const char* a = getenv("TW_TEST_SWEEP_FRAMES")) c->sw.frames = atoi(a) != 0;
     *out = c;
     return TW_OK;
 }
@@ -783,6 +789,9 @@ static int run_round(tw_shard* c, int n, int64_t t_end, uint64_t limit, uint32_t
             tw::SweepTab tab = c->sw.tab;
             if (sw->clean) {
                 tab.kill = cl.kill; tab.kwin = cl.kwin; tab.dirty = cl.dirty; tab.cflags = cl.cflags;
+                if (cl.bits && !c->sw.slow) {
+                    tab.eff = cl.eff; tab.bits = cl.bits; tab.excl = cl.excl ? 1u : 0u;
+                }
             }
             HIPCHK(sweep_launch(d, tab, st, sw->T, limit, sw->run_end, sw->seg));
             return TW_OK;
@@ -818,10 +827,12 @@ static int build_clean(tw_shard* c, const std::vector<tw::PrefixRow>& rows, cons
                                                sc + SC_RC0, c->sw.stub_h.data(), T);
     if (plan.slots.empty()) return TW_OK;
     const std::vector<uint32_t> tag = tw::clean_tags(L, rows.data(), rows.size(), plan.slots);
+    const tw::CleanEffects fx = tw::clean_effects(L, rows.data(), rows.size(), snap.data(), snap.size(),
+                                                  c->sw.stub_h.data(), plan);
     const size_t S4 = ((size_t)d.S + 3u) & ~(size_t)3u;
     const size_t o_win = sizeof(tw::KillEnt) * plan.ents.size(), o_tag = o_win + sizeof(tw::KillWin) * TW_RUNS,
                  o_dirty = o_tag + 4 * tag.size(), o_audit = (o_dirty + S4 + 4 * CF_COUNT + 7u) & ~(size_t)7u,
-                 total = o_audit + 8;
+                 o_eff = (o_audit + 8 + 15u) & ~(size_t)15u, total = o_eff + sizeof(tw::EffEnt) * fx.eff.size();
     Prefix::Snap::Clean& cl = sn.clean;
     if (hipMalloc(&cl.dev, total) != hipSuccess || hipHostMalloc((void**)&cl.h, S4 + 4 * CF_COUNT) != hipSuccess) {
         (void)hipGetLastError();  // (no memory: no skipping, not an error of the run)
@@ -831,7 +842,12 @@ static int build_clean(tw_shard* c, const std::vector<tw::PrefixRow>& rows, cons
     }
     uint8_t* b = (uint8_t*)cl.dev;
     HIPCHK(hipMemset(b, 0, total));
-    HIPCHK(hipMemcpy(b, plan.ents.data(), o_win, hipMemcpyHostToDevice));
+    {   // (the table with its positions' verdict bits, §3t)
+        std::vector<tw::KillEnt> ents = plan.ents;
+        for (size_t i = 0; i < ents.size() && !c->sw.frames; ++i)
+            ents[i].pad = (fx.eff[i].flags & tw::EFF_VERDICT) ? tw::KILL_VERDICT : 0u;
+        HIPCHK(hipMemcpy(b, ents.data(), o_win, hipMemcpyHostToDevice));
+    }
     HIPCHK(hipMemcpy(b + o_win, plan.win.data(), sizeof(tw::KillWin) * TW_RUNS, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(b + o_tag, tag.data(), 4 * tag.size(), hipMemcpyHostToDevice));
     std::memset(cl.h, 0, S4 + 4 * CF_COUNT);
@@ -841,6 +857,18 @@ static int build_clean(tw_shard* c, const std::vector<tw::PrefixRow>& rows, cons
     cl.dirty = b + o_dirty;
     cl.cflags = (uint32_t*)(b + o_dirty + S4);
     cl.audit = (unsigned long long*)(b + o_audit);
+    // the effects rows, and a clean bit per table position and replica: without
+    // the memory the sweep applies every entry the general way
+    HIPCHK(hipMemcpy(b + o_eff, fx.eff.data(), sizeof(tw::EffEnt) * fx.eff.size(), hipMemcpyHostToDevice));
+    cl.eff = (const tw::EffEnt*)(b + o_eff);
+    cl.excl = fx.exclusive;
+    const size_t bits = 8ull * plan.ents.size() * ((d.R + 63u) / 64u);
+    if (hipMalloc((void**)&cl.bits, bits) != hipSuccess) {
+        (void)hipGetLastError();
+        cl.bits = nullptr;
+    } else {
+        HIPCHK(hipMemset(cl.bits, 0, bits));
+    }
     cl.S = (uint32_t)S4;
     cl.stop = stop;
     cl.slots = plan.slots;
@@ -1057,6 +1085,7 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
     // do, and the sweep reports that no replica has work left.
     std::vector<Stop> stops;
     c->sw.last[0] = c->sw.last[1] = c->sw.last[2] = 0;
+    c->sw.path[0] = c->sw.path[1] = 0;
     c->sw.ms = 0.0;
     if (c->sw.on && c->sw.tab.stub && swept_order) {
         for (uint32_t i = 0; i < c->sw.times.size(); ++i) {
@@ -1081,6 +1110,7 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
         } else if (c->sw.h[SWS_FIRED] > seg) {
             c->sw.done |= 1u << stops[seg].ix;
             for (int k = 0; k < 3; ++k) c->sw.last[k] = c->sw.h[k];
+            c->sw.path[0] = c->sw.h[SWS_TERM]; c->sw.path[1] = c->sw.h[SWS_FAST];
             checked = checked || clean;
             ++seg;
             // the last stop swept and no replica has work left before t_end: done
@@ -1289,6 +1319,15 @@ int sh_sweep_stats(tw_shard* c, uint64_t* killers, uint64_t* victims, uint64_t* 
     if (victims) *victims = c->sw.last[1];
     if (refused) *refused = c->sw.last[2];
     if (ms) *ms = c->sw.ms;
+    return TW_OK;
+}
+
+int sh_sweep_path_stats(tw_shard* c, uint64_t* terminal, uint64_t* fast, uint64_t* slow) {
+    if (!c) return TW_ERR_INVALID;
+    if (!c->loaded) return TW_ERR_STATE;
+    if (terminal) *terminal = c->sw.path[0];
+    if (fast) *fast = c->sw.path[1];
+    if (slow) *slow = c->sw.last[0] - c->sw.path[1];
     return TW_OK;
 }
 

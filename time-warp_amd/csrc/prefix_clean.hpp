@@ -13,7 +13,9 @@
 // victim's (w2, w3).  A position is CLAIMABLE if it passes the static side of
 // validate's checks; the slots claimable positions name -- killer and victims
 // -- are the CLAIMED SLOTS, and a replica whose words at a position differ
-// from the table's marks that position's slots dirty.
+// from the table's marks that position's slots dirty.  The EFFECTS TABLE
+//  says, per position, what its pops do: where a replica's words
+// are the table's, the sweep applies them without loading a header.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -54,6 +56,9 @@ struct KillEnt {
     uint32_t vw[4];   // victim 0's w2, w3; victim 1's
 };
 static_assert(sizeof(KillEnt) == 64, "KillEnt is four quads");
+// KillEnt::pad of the table on the device: the position's EFF_VERDICT (below),
+// where validate has the word in registers anyway (set by the host's glue)
+constexpr uint32_t KILL_VERDICT = 1u;
 
 // A run's table window: ring positions [pos0, pos0 + n) (it may wrap), whose
 // entries are `base`, `base + 1`, .. of the table.
@@ -160,6 +165,146 @@ inline CleanPlan clean_build(const CleanLayout& L, const PrefixRow* rows, size_t
     for (uint32_t s = 0; s < L.S; ++s)
         if (claimed[s]) p.slots.push_back(s);
     return p;
+}
+
+// The header fields the effects table reads (tw_dev.hpp's F_STARTED, F_OWNS and
+// TW_EXC_THREAD_KILLED: sweep.hip asserts that they agree)
+constexpr uint32_t PCL_F_STARTED = 1u, PCL_F_OWNS = 8u, PCL_EXC_THREAD_KILLED = 1u;
+
+// What a claimable position's pops do, from the snapshot alone:
+// one row per table position, parallel to CleanPlan::ents, eight quads.  The
+// sweep reads the first four of a position whose words validate found equal
+// to the table's: by §3o's claim, extended to w0 and w1, the replica's three
+// headers are then the snapshot's and the row says everything apply would
+// have learnt from them.
+constexpr uint32_t EFF_VERDICT = 1u;  // every victim passes validate's static checks
+constexpr uint32_t EFF_EXCL = 2u;     // no victim named by another position's recorded refs, or twice here
+constexpr uint32_t EFF_NADD_SHIFT = 8u, EFF_NREL_SHIFT = 12u;  // counts, 0 - 3 each
+struct EffEnt {
+    uint32_t flags;         // EFF_* | adds << EFF_NADD_SHIFT | releases << EFF_NREL_SHIFT (0: not claimable)
+    uint32_t pc;            // the killer's resume pc: add 0 carries term0(T, RESUME | pc)
+    uint32_t add_node[3];   // the hash adds, merged per node as tw_sweep_apply merges them;
+    uint32_t add_kills[3];  // ... add 0 is the killer's node; ThreadKilled terms in each
+    uint32_t rel_node[3];   // the owned listeners released (bind_rel[node] = tid), killer first
+    uint32_t pad0;
+    uint32_t rel_tid[3];
+    uint32_t pad1;
+    // (the next nine words: what a store of the dead headers would need; no
+    // kernel reads them -- the fast entry of a surviving replica is not built, §3t)
+    uint32_t slot[3];       // killer, victim 0, victim 1 (unused: 0)
+    uint32_t w0[3];         // their snapshot headers' w0 (pc, frames, flags, pending exception)
+    uint32_t w1[3];         // ... and w1 (node)
+    uint32_t pad2[2];
+    // Every position whose snapshot killer is a kill wake, claimable or not (a
+    // killer in slot 0 is not): the refs its registers hold, (slot, tid) each.
+    // A replica whose refs at a position are these is bound to the table there
+    // without its killer's (w2, w3) being compared.
+    uint32_t nxref;
+    uint32_t xref[4];
+};
+static_assert(sizeof(EffEnt) == 128, "EffEnt is eight quads");
+
+struct CleanEffects {
+    std::vector<EffEnt> eff;  // [CleanPlan::ents.size()]
+    bool exclusive = false;   // some position is claimable and no slot is named twice by the recorded refs
+};
+
+// The effects table of a kill table built from the same snapshot and stub words.
+inline CleanEffects clean_effects(const CleanLayout& L, const PrefixRow* rows, size_t n_rows, const uint8_t* snap,
+                                  size_t snap_bytes, const uint32_t* stub, const CleanPlan& p) {
+    CleanEffects out;
+    out.eff.assign(p.ents.size(), EffEnt{});
+    if (!rows || !snap || !stub || L.R == 0) return out;
+    std::unordered_map<uint64_t, uint32_t> at;
+    for (size_t i = 0; i < n_rows; ++i)
+        if (rows[i].es == 16 && (uint64_t)rows[i].off + 16 <= snap_bytes) at.emplace(rows[i].dst, rows[i].off);
+    struct Quad { uint32_t x, y, z, w; };
+    auto rec = [&](uint32_t slot, uint32_t qd, Quad& q) {
+        if (slot >= L.S) return false;
+        auto it = at.find(L.slots + ((uint64_t)qd * L.RQ + (uint64_t)slot * L.R) * 16u);
+        if (it == at.end()) return false;
+        std::memcpy(&q, snap + it->second, 16);
+        return true;
+    };
+    auto reg_of = [](const Quad& q2, const Quad& q3, uint32_t i) {
+        const uint32_t lo = i == 0 ? q2.x : i == 1 ? q2.z : i == 2 ? q3.x : q3.z;
+        const uint32_t hi = i == 0 ? q2.y : i == 1 ? q2.w : i == 2 ? q3.y : q3.w;
+        return ((uint64_t)hi << 32) | lo;
+    };
+    // the refs of every position (a claimable one's are the kill table's), and
+    // how often they name each slot
+    std::vector<uint32_t> named(L.S, 0);
+    for (size_t i = 0; i < p.ents.size(); ++i) {
+        const KillEnt& k = p.ents[i];
+        EffEnt& o = out.eff[i];
+        if (k.nref >= 1 && k.nref <= 2) {
+            o.nxref = k.nref;
+            for (uint32_t w = 0; w < 4; ++w) o.xref[w] = k.ref[w];
+        } else {
+            Quad h, q2, q3;
+            if (k.nref != 0 || !rec(k.e[2], 0, h) || !rec(k.e[2], 2, q2) || !rec(k.e[2], 3, q3)) continue;
+            const uint32_t pc = h.x & 0xFFFFu, sw = stub[pc < L.n_insns ? pc : L.n_insns];
+            if (h.w != k.e[3] || h.w == 0 || !(sw & SWB_VALID)) continue;
+            o.nxref = (sw & SWB_TWO) ? 2u : 1u;
+            const uint64_t r0 = reg_of(q2, q3, SWB_RA0(sw)), r1 = o.nxref > 1 ? reg_of(q2, q3, SWB_RA1(sw)) : 0ull;
+            o.xref[0] = (uint32_t)r0; o.xref[1] = (uint32_t)(r0 >> 32);
+            o.xref[2] = (uint32_t)r1; o.xref[3] = (uint32_t)(r1 >> 32);
+        }
+        for (uint32_t v = 0; v < o.nxref; ++v)
+            if (o.xref[2 * v] < L.S) ++named[o.xref[2 * v]];
+    }
+    uint32_t claimable = 0;
+    bool all = true;
+    for (size_t i = 0; i < p.ents.size(); ++i) {
+        const KillEnt& k = p.ents[i];
+        EffEnt& o = out.eff[i];
+        if (k.nref == 0 || k.nref > 2) continue;
+        Quad h[3];
+        bool have = rec(k.e[2], 0, h[0]);
+        for (uint32_t v = 0; v < k.nref; ++v) have = have && rec(k.ref[2 * v], 0, h[1 + v]);
+        if (!have) { all = false; continue; }  // (clean_build read the same rows: cannot happen)
+        ++claimable;
+        o.slot[0] = k.e[2];
+        for (uint32_t v = 0; v < k.nref; ++v) o.slot[1 + v] = k.ref[2 * v];
+        for (uint32_t s = 0; s <= k.nref; ++s) { o.w0[s] = h[s].x; o.w1[s] = h[s].y; }
+        o.pc = h[0].x & 0xFFFFu;
+        // the adds: the killer's node first, with the victims on it; the others
+        // as one add where they share a node (sweep.hip: m0, m1, s0, s1, both)
+        const uint32_t kn = h[0].y, n0 = h[1].y, n1 = k.nref > 1 ? h[2].y : 0u;
+        const bool c1 = k.nref > 1, m0 = n0 == kn, m1 = c1 && n1 == kn;
+        uint32_t na = 1;
+        o.add_node[0] = kn;
+        o.add_kills[0] = (m0 ? 1u : 0u) + (m1 ? 1u : 0u);
+        const bool s0 = !m0, s1 = c1 && !m1, both = s0 && s1 && n0 == n1;
+        if (s0) { o.add_node[na] = n0; o.add_kills[na] = both ? 2u : 1u; ++na; }
+        if (s1 && !both) { o.add_node[na] = n1; o.add_kills[na] = 1u; ++na; }
+        uint32_t nr = 0;
+        for (uint32_t s = 0; s <= k.nref; ++s)
+            if (((h[s].x >> PCL_FL_SHIFT) & 0x3Fu) & PCL_F_OWNS) { o.rel_node[nr] = h[s].y; o.rel_tid[nr] = h[s].z; ++nr; }
+        bool verdict = true, excl = true;  // (exclusive among all positions' refs, claimable or not)
+        for (uint32_t v = 0; v < k.nref; ++v) {
+            const Quad& vh = h[1 + v];
+            const uint32_t fl = (vh.x >> PCL_FL_SHIFT) & 0x3Fu, nfr = (vh.x >> 16) & 15u, pc = vh.x & 0xFFFFu;
+            bool ok = (fl & PCL_F_STARTED) && !(fl & PCL_F_MAIN) && (vh.x >> PCL_EXC_SHIFT) == 0 && nfr <= 2 &&
+                      vh.w != 0 && vh.y < L.N && stub[pc < L.n_insns ? pc : L.n_insns] == 0;
+            Quad f{0u, 0u, 0u, 0u};
+            if (ok && nfr) {
+                ok = rec(o.slot[1 + v], 1, f);
+                const uint32_t f0 = f.x >> 16, f1 = nfr > 1 ? f.y >> 16 : 0xFFFFu;
+                ok = ok && f0 != 0 && f1 != 0 && !((f0 | (nfr > 1 ? f1 : 0u)) & (1u << PCL_EXC_THREAD_KILLED));
+            }
+            verdict = verdict && ok;
+            excl = excl && named[o.slot[1 + v]] == 1;
+        }
+        all = all && excl;
+        o.flags = (verdict ? EFF_VERDICT : 0u) | (excl ? EFF_EXCL : 0u) | (na << EFF_NADD_SHIFT) | (nr << EFF_NREL_SHIFT);
+    }
+    // A table-bound replica trusts the recorded refs of positions that are not
+    // claimable too (validate takes them for the table's), so the table-wide
+    // flag speaks of every recorded ref: no slot named twice, by whatever position.
+    for (uint32_t s = 0; s < L.S; ++s) all = all && named[s] <= 1;
+    out.exclusive = claimable != 0 && all;
+    return out;
 }
 
 // The tag of every directory row: the slot whose quad 1, 2 or 3 it is when that

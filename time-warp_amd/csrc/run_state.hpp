@@ -85,12 +85,16 @@ struct Sweep {
     uint32_t done = 0;
     unsigned long long* h = nullptr;    // pinned; outlives loads
     uint64_t last[3] = {0, 0, 0};
+    uint64_t path[2] = {0, 0};          // ... its terminal replicas and effects-table entries (§3t)
     double ms = 0.0;                    // device time of the last tw_run's sweeps
+    bool slow = false;                  // the testing hook TW_TEST_SWEEP_SLOW (read when the context is made)
+    bool frames = false;                // ... and TW_TEST_SWEEP_FRAMES
 
     void unload() {
         Sweep z;
-        z.h = h; z.ms = ms;
+        z.h = h; z.ms = ms; z.slow = slow; z.frames = frames;
         for (int k = 0; k < 3; ++k) z.last[k] = last[k];
+        for (int k = 0; k < 2; ++k) z.path[k] = path[k];
         *this = z;
     }
     void destroy() {
@@ -130,6 +134,11 @@ struct Prefix {
             uint32_t* cflags = nullptr;
             unsigned long long* audit = nullptr;
             uint8_t* h = nullptr;               // pinned: [S] dirty bytes + flag words
+            // the sweep's terminal path (§3t): the effects rows (in `dev`) and the
+            // clean bits, a block of their own; bits null: no memory, no such path
+            const tw::EffEnt* eff = nullptr;
+            unsigned long long* bits = nullptr;
+            bool excl = false;
             uint32_t S = 0, stop = 0;
             std::vector<uint32_t> slots;        // the claimed slots
         } clean;
@@ -156,6 +165,7 @@ struct Prefix {
         if (snap.tab.rows) (void)hipFree((void*)snap.tab.rows);
         if (snap.tab.snap) (void)hipFree(snap.tab.snap);
         if (snap.clean.dev) (void)hipFree(snap.clean.dev);
+        if (snap.clean.bits) (void)hipFree(snap.clean.bits);
         if (snap.clean.h) (void)hipHostFree(snap.clean.h);
         snap = Snap{};
         touch();

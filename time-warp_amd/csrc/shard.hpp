@@ -36,6 +36,7 @@ TW_HIDDEN int sh_set_tie_mode(tw_shard* c, uint32_t mode);
 // the sweep kernels' device time
 TW_HIDDEN int sh_set_sweep(tw_shard* c, int on);
 TW_HIDDEN int sh_sweep_stats(tw_shard* c, uint64_t* killers, uint64_t* victims, uint64_t* refused, double* ms);
+TW_HIDDEN int sh_sweep_path_stats(tw_shard* c, uint64_t* terminal, uint64_t* fast, uint64_t* slow);
 // the send-free prefix (prefix.hip): the switch; the image's T0, the cached
 // snapshot's events and bytes per replica (0: none), what the last sh_run did
 // (TW_PREFIX_*) and its apply's device time

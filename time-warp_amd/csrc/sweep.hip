@@ -14,6 +14,8 @@
 //   validate  read-only, per entry: a live kill-stub wake whose refs are stale
 //             or name plain victims (see below); counts killers and throwTos
 //   apply     per entry, replicas that passed: what the pops would have left
+//             (replicas the sweep ends: tw_sweep_apply_term, only what is
+//             still read of them -- hash terms, listener releases; §3t)
 //   finalize  per replica: the scalar words, run heads, free-stack top
 //
 // A replica that fails any check is left exactly as it was and takes the
@@ -187,6 +189,18 @@ __device__ __forceinline__ bool load_killer(const Dev& c, const SweepTab& t, uin
     return true;
 }
 
+// whether the entry's refs are the ones the effects table recorded for its
+// position (§3t; rare)
+__device__ __forceinline__ bool refs_recorded(const Dev& c, const SweepTab& t, const Killer& k, uint32_t pos,
+                                           const KillWin& kw) {
+    const uint32_t tk = pos >= kw.pos0 ? pos - kw.pos0 : pos + c.Cr - kw.pos0;
+    if (!t.eff || tk >= kw.n) return false;
+    const uint4 GAS* ep = (const uint4 GAS*)gp(t.eff) + (size_t)(kw.base + tk) * 8u;
+    const uint4 x = ep[7];
+    if (ep[6].w != k.nref || x.x != (uint32_t)k.ref0 || x.y != (uint32_t)(k.ref0 >> 32)) return false;
+    return k.nref < 2u || (x.z == (uint32_t)k.ref1 && x.w == (uint32_t)(k.ref1 >> 32));
+}
+
 // a dying thread's owned listener is released by one store (Lane::rel_bind);
 // with several dying owners of one node the last store would win, so only the
 // node's current owner may die in a sweep
@@ -196,7 +210,10 @@ __device__ __forceinline__ bool owner_ok(const Dev& c, uint32_t r, uint4 h) {
 }
 
 // ------------------------------------------------------------------ validate
-__global__ void __launch_bounds__(64) tw_sweep_validate(Dev c, SweepTab t, int64_t T, uint32_t expect) {
+// (pinned to 8 waves per SIMD: left alone the compiler takes 102 scalar
+// registers, which is 7 waves; so it keeps some in lanes of a vector register)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
+tw_sweep_validate(Dev c, SweepTab t, int64_t T, uint32_t expect) {
     const uint32_t r = blockIdx.x * 64 + threadIdx.x;
     if (r >= c.R || !sweep_gate(c, t, expect)) return;
     if (*acc_at(t, c, SW_BAD, r)) return;
@@ -213,6 +230,8 @@ __global__ void __launch_bounds__(64) tw_sweep_validate(Dev c, SweepTab t, int64
             const uint32_t off = kw.pos0 >= rh ? kw.pos0 - rh : kw.pos0 + c.Cr - rh;
             if ((uint64_t)off + kw.n > pl) gp(t.cflags)[CF_ALL_DIRTY] = 1u;
         }
+        // (§3t: the clean bits are keyed by the loop's own index -- entry i of a
+        // run whose head is the window's start is table position kw.base + i)
         for (uint32_t i = blockIdx.y; i < pl && !bad; i += gridDim.y) {
             uint32_t pos = rh + i;
             pos = pos >= c.Cr ? pos - c.Cr : pos;
@@ -247,7 +266,12 @@ __global__ void __launch_bounds__(64) tw_sweep_validate(Dev c, SweepTab t, int64
                 const uint32_t fl = (h.x >> FL_SHIFT) & 0x3Fu, nfr = (h.x >> 16) & 15u, pc = h.x & 0xFFFFu;
                 bool ok = (fl & F_STARTED) && !(fl & F_MAIN) && (h.x >> EXC_SHIFT) == 0 && nfr <= 2 && h.w != 0 &&
                           h.y < c.N && gp(t.stub)[pc < c.n_insns ? pc : c.n_insns] == 0 && owner_ok(c, r, h);
-                if (ok && nfr) {
+                // (§3t) a victim whose (w2, w3) are the table's has the snapshot's
+                // frames quad (§3o), and the table's verdict bit says that the
+                // snapshot's passes: the quad is not loaded
+                const bool stat =
+                    tab && (ka.w & KILL_VERDICT) != 0u && h.z == (v ? kv.z : kv.x) && h.w == (v ? kv.w : kv.y);
+                if (ok && nfr && !stat) {
                     // neither a finally frame (mask 0) nor one catching ThreadKilled
                     const uint4 f = *rec_q(c, ts, r, 1);
                     const uint32_t m0 = f.x >> 16, m1 = nfr > 1 ? f.y >> 16 : 0xFFFFu;
@@ -260,6 +284,19 @@ __global__ void __launch_bounds__(64) tw_sweep_validate(Dev c, SweepTab t, int64
                 gp(t.dirty)[kslot] = 1;
                 gp(t.dirty)[kr.x] = 1;
                 if (ka.z > 1u) gp(t.dirty)[kr.z] = 1;
+            }
+            // Refs that came from the registers (no table hit: the observer's kill
+            // wake in slot 0, a killer forked since the snapshot) bind the replica
+            // to the table only if they are the refs recorded for the position.
+            // (every wave of the replica that sees others stores the same word;
+            // without the clean bits nobody reads it: sweep_term)
+            if (t.bits && !(tab && k.hit) && !refs_recorded(c, t, k, pos, kw)) *acc_at(t, c, SW_NOTAB, r) = 1u;
+            if (t.bits && i < kw.n) {
+                // one ballot per wave and position, stored by every lane that is
+                // here: one address, one value (a lane that left the loop, or
+                // never had entry i, is not clean)
+                const unsigned long long cb = __ballot(tab && !mis && !bad && rh == kw.pos0);
+                gp(t.bits)[(size_t)(kw.base + i) * gridDim.x + blockIdx.x] = cb;
             }
         }
     }
@@ -283,12 +320,103 @@ __device__ __forceinline__ bool sweep_go(const Dev& c, const SweepTab& t, uint32
     return k != 0 && ev + k + h <= max_events && sq + h < (uint64_t)seq_limit(c);
 }
 
+// A TERMINAL replica (§3t), of those sweep_go passes: every ref of its sweep is
+// a ref of the kill table (SW_NOTAB clear), the table names no victim twice,
+// and every thread it has left is a kill wake of the sweep or a victim one of
+// them hits.  Then each hit is a victim of its own, V = H, and the sweep ends
+// the replica: live reaches 0, the status becomes DONE, and nothing reads its
+// thread records or its free stack before the next tw_reset.
+__device__ __forceinline__ bool sweep_term(const Dev& c, const SweepTab& t, uint32_t r) {
+    if (!t.bits || !t.excl || *acc_at(t, c, SW_NOTAB, r)) return false;
+    const uint64_t k = *acc_at(t, c, SW_K, r), h = *acc_at(t, c, SW_H, r);
+    return gp(c.scal)[(size_t)SC_LIVE * c.R + r] == k + h;
+}
+
+constexpr uint32_t NONE = 0xFFFFFFFFu;  // a ref without a live victim
+static_assert(PCL_F_STARTED == F_STARTED && PCL_F_OWNS == F_OWNS && PCL_EXC_THREAD_KILLED == TW_EXC_THREAD_KILLED &&
+                  PCL_FL_SHIFT == FL_SHIFT && PCL_EXC_SHIFT == EXC_SHIFT && PCL_F_MAIN == F_MAIN,
+              "prefix_clean.hpp reads the header as tw_dev.hpp lays it out");
+
+// ------------------------------------------------------- apply, terminal path
+// What the pops of a terminal replica leave that anything still reads: the
+// hash terms, the released listeners and the count of victims.  No header
+// store, no claim swap, no free-stack append.  An entry whose clean bit is set
+// takes all of it from the effects row; any other loads the headers as
+// tw_sweep_apply does, and stores nothing else either.
+__global__ void __launch_bounds__(64) tw_sweep_apply_term(Dev c, SweepTab t, int64_t T, uint64_t max_events,
+                                                           uint32_t expect) {
+    const uint32_t r = blockIdx.x * 64 + threadIdx.x;
+    if (r >= c.R || !sweep_gate(c, t, expect)) return;
+    if (!sweep_go(c, t, r, max_events) || !sweep_term(c, t, r)) return;
+    const size_t R = c.R;
+    const uint64_t GAS* sc = gp(c.scal) + r;
+    const uint64_t vterm = term0(T, TW_KIND_EXC | TW_EXC_THREAD_KILLED);
+    auto hash_add = [&](uint32_t node, unsigned long long x) {
+        __hip_atomic_fetch_add((unsigned long long GAS*)(gp(c.hash) + (size_t)node * R + r), x, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    };
+    uint32_t nv = 0, nfast = 0;
+    for (uint32_t j = 0; j < TW_RUNS; ++j) {
+        const uint32_t pl = *acc_at(t, c, SW_PL0 + j, r), rh = (uint32_t)sc[(SC_RH0 + j) * R];
+        const KillWin kw = kill_win(t, j);
+        const bool at0 = kw.n != 0u && rh == kw.pos0;
+        for (uint32_t i = blockIdx.y; i < pl; i += gridDim.y) {
+            bool clean = false;
+            if (at0 && i < kw.n)
+                clean = ((gp(t.bits)[(size_t)(kw.base + i) * gridDim.x + blockIdx.x] >> threadIdx.x) & 1ull) != 0ull;
+            if (clean) {
+                const uint4 GAS* ep = (const uint4 GAS*)gp(t.eff) + (size_t)(kw.base + i) * 8u;
+                const uint4 a = ep[0], b = ep[1];  // flags, pc, add_node[0..1]; add_node[2], add_kills[0..2]
+                const uint32_t na = (a.x >> EFF_NADD_SHIFT) & 15u, nr = (a.x >> EFF_NREL_SHIFT) & 15u;
+                hash_add(a.z, term0(T, TW_KIND_RESUME | a.y) + (unsigned long long)b.y * vterm);
+                if (na > 1u) hash_add(a.w, (unsigned long long)b.z * vterm);
+                if (na > 2u) hash_add(b.x, (unsigned long long)b.w * vterm);
+                if (nr) {
+                    const uint4 rn = ep[2], rt = ep[3];
+                    gp(c.bind_rel)[(size_t)rn.x * R + r] = rt.x;
+                    if (nr > 1u) gp(c.bind_rel)[(size_t)rn.y * R + r] = rt.y;
+                    if (nr > 2u) gp(c.bind_rel)[(size_t)rn.z * R + r] = rt.z;
+                }
+                nv += b.y + b.z + b.w;
+                ++nfast;
+                continue;
+            }
+            uint32_t pos = rh + i;
+            pos = pos >= c.Cr ? pos - c.Cr : pos;
+            const uint4 e = *run_ent(c, j, pos, r);
+            Killer k;
+            if (!load_killer<false>(c, t, r, e, T, k, pos, kw)) continue;  // (validated: cannot happen)
+            if (((k.h.x >> FL_SHIFT) & 0x3Fu) & F_OWNS) gp(c.bind_rel)[(size_t)k.h.y * R + r] = k.h.z;
+            // a live victim is this ref's alone (table-bound, exclusive): no claim
+            auto hit = [&](uint64_t ref) -> uint32_t {
+                const uint32_t ts = (uint32_t)ref, tid = (uint32_t)(ref >> 32);
+                if (ts >= c.S) return NONE;
+                const uint4 h = *rec_q(c, ts, r, 0);
+                if (h.z != tid) return NONE;
+                if (((h.x >> FL_SHIFT) & 0x3Fu) & F_OWNS) gp(c.bind_rel)[(size_t)h.y * R + r] = tid;
+                return h.y;
+            };
+            const uint32_t n0 = hit(k.ref0);
+            const uint32_t n1 = k.nref > 1 ? hit(k.ref1) : NONE;
+            const bool c0 = n0 != NONE, c1 = n1 != NONE;
+            const bool m0 = c0 && n0 == k.h.y, m1 = c1 && n1 == k.h.y;
+            hash_add(k.h.y, term0(T, TW_KIND_RESUME | (k.h.x & 0xFFFFu)) + (m0 ? vterm : 0ull) + (m1 ? vterm : 0ull));
+            const bool s0 = c0 && !m0, s1 = c1 && !m1, both = s0 && s1 && n0 == n1;
+            if (s0) hash_add(n0, both ? 2ull * vterm : vterm);
+            if (s1 && !both) hash_add(n1, vterm);
+            nv += (c0 ? 1u : 0u) + (c1 ? 1u : 0u);
+        }
+    }
+    if (nv) __hip_atomic_fetch_add(acc_at(t, c, SW_V, r), nv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (nfast) __hip_atomic_fetch_add(acc_at(t, c, SW_FAST, r), nfast, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // --------------------------------------------------------------------- apply
 __global__ void __launch_bounds__(64) tw_sweep_apply(Dev c, SweepTab t, int64_t T, uint64_t max_events,
                                                       uint32_t expect) {
     const uint32_t r = blockIdx.x * 64 + threadIdx.x;
     if (r >= c.R || !sweep_gate(c, t, expect)) return;
-    if (!sweep_go(c, t, r, max_events)) return;
+    if (!sweep_go(c, t, r, max_events) || sweep_term(c, t, r)) return;
     const size_t R = c.R;
     const uint64_t GAS* sc = gp(c.scal) + r;
     const uint32_t fn0 = (uint32_t)sc[SC_FREE_N * R];
@@ -308,7 +436,6 @@ __global__ void __launch_bounds__(64) tw_sweep_apply(Dev c, SweepTab t, int64_t 
             *rec_q(c, e.z, r, 0) = make_uint4(k.h.x | (F_STARTED << FL_SHIFT), k.h.y, 0xFFFFFFFFu, 0u);
             // the victim dies once: whoever takes its queued seq owns its pop
             // (returns the victim's node, NONE for a ref that is stale or another killer's)
-            constexpr uint32_t NONE = 0xFFFFFFFFu;
             auto claim = [&](uint64_t ref) -> uint32_t {
                 const uint32_t ts = (uint32_t)ref, tid = (uint32_t)(ref >> 32);
                 if (ts >= c.S) return NONE;
@@ -359,7 +486,7 @@ __global__ void __launch_bounds__(256) tw_sweep_finalize(Dev c, SweepTab t, int6
                                                           int64_t t_end, uint32_t expect) {
     const uint32_t r = blockIdx.x * 256 + threadIdx.x;
     if (!sweep_gate(c, t, expect)) return;
-    unsigned long long k = 0, v = 0, ref = 0, rem = 0;
+    unsigned long long k = 0, v = 0, ref = 0, rem = 0, term = 0, fast = 0;
     if (r < c.R) {
         const size_t R = c.R;
         uint64_t GAS* sc = gp(c.scal) + r;
@@ -367,6 +494,8 @@ __global__ void __launch_bounds__(256) tw_sweep_finalize(Dev c, SweepTab t, int6
         // the replica's next event, for the count of replicas a later launch has work for
         int64_t next = (int64_t)(((uint64_t)*acc_at(t, c, SW_XHI, r) << 32) | *acc_at(t, c, SW_XLO, r));
         if (sweep_go(c, t, r, max_events)) {
+            term = sweep_term(c, t, r) ? 1ull : 0ull;  // (as both applies saw it: live is still the event kernel's)
+            fast = *acc_at(t, c, SW_FAST, r);
             k = *acc_at(t, c, SW_K, r);
             v = *acc_at(t, c, SW_V, r);
             const uint32_t h = *acc_at(t, c, SW_H, r), m = *acc_at(t, c, SW_FREE, r);
@@ -411,12 +540,16 @@ __global__ void __launch_bounds__(256) tw_sweep_finalize(Dev c, SweepTab t, int6
         v += __shfl_xor(v, m, 64);
         ref += __shfl_xor(ref, m, 64);
         rem += __shfl_xor(rem, m, 64);
+        term += __shfl_xor(term, m, 64);
+        fast += __shfl_xor(fast, m, 64);
     }
     if ((threadIdx.x & 63u) == 0) {
         if (k) __hip_atomic_fetch_add(gp(t.stats) + 0, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (v) __hip_atomic_fetch_add(gp(t.stats) + 1, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (ref) __hip_atomic_fetch_add(gp(t.stats) + 2, ref, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (rem) __hip_atomic_fetch_add(gp(t.stats) + SWS_LEFT, rem, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (term) __hip_atomic_fetch_add(gp(t.stats) + SWS_TERM, term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (fast) __hip_atomic_fetch_add(gp(t.stats) + SWS_FAST, fast, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -444,6 +577,8 @@ hipError_t sweep_launch(const Dev& d, const SweepTab& t, hipStream_t st, int64_t
     const dim3 gr((d.R + 255u) / 256u), ge(groups, chunks);
     hipLaunchKernelGGL(tw_sweep_scan, gr, dim3(256), 0, st, d, t, T, expect);
     hipLaunchKernelGGL(tw_sweep_validate, ge, dim3(64), 0, st, d, t, T, expect);
+    // (each replica is one kernel's: the terminal path's or the general one's)
+    if (t.bits) hipLaunchKernelGGL(tw_sweep_apply_term, ge, dim3(64), 0, st, d, t, T, max_events, expect);
     hipLaunchKernelGGL(tw_sweep_apply, ge, dim3(64), 0, st, d, t, T, max_events, expect);
     hipLaunchKernelGGL(tw_sweep_finalize, gr, dim3(256), 0, st, d, t, T, max_events, t_end, expect);
     hipLaunchKernelGGL(tw_sweep_mark, dim3(1), dim3(1), 0, st, d, t, expect);

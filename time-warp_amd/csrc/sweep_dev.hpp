@@ -15,12 +15,16 @@ namespace tw {
 // per-replica accumulator words, [SW_*][R] u32, cleared by the scan:
 // SW_BAD 0 swept so far / 1 refused / 2 nothing to sweep; killers, throwTos
 // that hit a live victim, victims claimed, slots freed, the replica's next
-// event outside the swept prefixes (two words), prefix length per run
-enum { SW_BAD, SW_K, SW_H, SW_V, SW_FREE, SW_XLO, SW_XHI, SW_PL0, SW_COUNT = SW_PL0 + TW_RUNS };
+// event outside the swept prefixes (two words), prefix length per run; then
+// SW_NOTAB: some entry's refs came from its registers, not from the kill table
+// (clear: the replica is table-bound, §3t); SW_FAST: entries applied from the
+// effects table alone
+enum { SW_BAD, SW_K, SW_H, SW_V, SW_FREE, SW_XLO, SW_XHI, SW_PL0, SW_NOTAB = SW_PL0 + TW_RUNS, SW_FAST, SW_COUNT };
 // Sweep words of a tw_run, SweepTab::stats: kill wakes, victims and refused
 // replicas; how many of the run's stops have been swept; replicas a later
-// launch still has work for, as of the last sweep
-enum { SWS_KILLERS, SWS_VICTIMS, SWS_REFUSED, SWS_FIRED, SWS_LEFT, SWS_COUNT };
+// launch still has work for, as of the last sweep; replicas swept on the
+// terminal path and entries applied from the effects table alone (§3t)
+enum { SWS_KILLERS, SWS_VICTIMS, SWS_REFUSED, SWS_FIRED, SWS_LEFT, SWS_TERM, SWS_FAST, SWS_COUNT };
 
 struct SweepTab {
     const uint32_t* stub;       // [n_insns + 1] stub word of each resume pc (sweep_classify.hpp)
@@ -33,6 +37,11 @@ struct SweepTab {
     const KillWin* kwin;        // [TW_RUNS] each run's window of them
     uint8_t* dirty;             // [S] a claimed slot some replica's words did not match
     uint32_t* cflags;           // [CF_COUNT] (prefix_dev.hpp)
+    // The table's effects rows and the clean bits validate publishes for apply
+    // (DESIGN §3t); bits null: no terminal path, the sweep as in §3o.
+    const EffEnt* eff;          // parallel to `kill`
+    unsigned long long* bits;   // [table position][R / 64]: one ballot per wave and position
+    uint32_t excl;              // every claimable position is exclusive
 };
 
 // The parked layout the event kernel's epilogue leaves (shared with prefix.hip):

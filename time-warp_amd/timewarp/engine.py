@@ -34,7 +34,7 @@ EXPORTS = ["tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_ru
            "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms", "tw_set_sweep", "tw_sweep_stats",
            "tw_set_prefix", "tw_prefix_stats", "tw_set_measure_keys", "tw_measure_phases_ms",
            "tw_prefix_clean_stats", "tw_set_trace_batch", "tw_lp_set_trace", "tw_lp_read_trace", "tw_lp_measure",
-           "tw_set_live_delays", "tw_live_stats"]
+           "tw_set_live_delays", "tw_live_stats", "tw_sweep_path_stats"]
 GEOMETRIES = ("dense", "sparse", "half", "wave", "lp", "narrow", "lpb", "compact")  # TW_GEO_* order
 
 # tw_trace_rec (include/timewarp.h)
@@ -127,6 +127,9 @@ def load_library(path: Optional[str] = None):
         lib.tw_prefix_clean_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         lib.tw_prefix_clean_stats.restype = C.c_int
+    if hasattr(lib, "tw_sweep_path_stats"):  # (an older in-tree build under TW_LIB lacks it)
+        lib.tw_sweep_path_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
+        lib.tw_sweep_path_stats.restype = C.c_int
     if hasattr(lib, "tw_lp_set_trace"):  # (an older in-tree build under TW_LIB lacks them)
         lib.tw_lp_set_trace.argtypes = [C.c_void_p, C.c_uint32]
         lib.tw_lp_read_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
@@ -375,6 +378,14 @@ class Engine:
         k, v, f = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         _check(self.lib.tw_sweep_stats(self.ctx, C.byref(k), C.byref(v), C.byref(f)), "tw_sweep_stats")
         return {"killers": int(k.value), "victims": int(v.value), "refused_replicas": int(f.value)}
+
+    def sweep_path_stats(self) -> dict:
+        """Of the last run's sweeps: replicas swept on the terminal path, kill
+        wakes applied from the effects table alone (fast) and with their
+        headers loaded (slow) (tw_sweep_path_stats)."""
+        t, f, s = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(self.lib.tw_sweep_path_stats(self.ctx, C.byref(t), C.byref(f), C.byref(s)), "tw_sweep_path_stats")
+        return {"terminal_replicas": int(t.value), "fast_entries": int(f.value), "slow_entries": int(s.value)}
 
     PREFIX_USE = ("not_eligible", "piloted", "applied", "refused")  # tw_prefix_use
 
