@@ -510,6 +510,61 @@ int tw_measure_ms(tw_ctx* ctx, double* kernel_ms);
  * run).  Writes min(cap, 7) entries and returns how many. */
 int tw_measure_phases_ms(tw_ctx* ctx, double* ms, size_t cap);
 
+/* Exact order statistics of one latency: what the reference's
+ * bench/calc-template.ods takes as MEDIAN over measures.csv's rows, and any
+ * other percentile, without reading a trace back.
+ *
+ * For a latency (tag_from != tag_to) a replica's pairs are exactly tw_measure's:
+ * the ids with one record of each tag among the kept records; a truncated
+ * replica contributes nothing but `truncated`.  The pair latencies d are the
+ * two's complement of t_to - t_from in 64 bits, sorted ascending as signed
+ * values.  A quantile is given in parts per million, q_ppm in 0 .. 1,000,000;
+ * with n pairs and pos = q_ppm * (n - 1):
+ *     lo_us = d[pos div 10^6]
+ *     hi_us = d[pos div 10^6 + (pos mod 10^6 != 0)]
+ * and n == 0 gives lo_us = INT64_MAX, hi_us = INT64_MIN (as min_us / max_us).
+ * So q_ppm = 0 is the minimum, 1,000,000 the maximum, and the spreadsheet's
+ * MEDIAN is (lo_us + hi_us) / 2 at 500,000: the mean of the two middle values
+ * for an even n.  pos is not formed as one product: the indices are exact for
+ * every n up to 2^64 - 1 (csrc/measure_select.hpp, qs_index).
+ *
+ * total: n_q entries over all pairs of the batch, or NULL; per_replica:
+ * [n][n_q], replica-major, or NULL (n = 0, or the context's replica count);
+ * pairs / truncated: the batch's counts as tw_measure's, either may be NULL.
+ * Blocking, stream-ordered after the last tw_run; changes no state and may be
+ * called repeatedly, and between calls of tw_measure.  Statuses as tw_measure's:
+ * TW_ERR_STATE when nothing is loaded or tracing is off; TW_ERR_INVALID for a
+ * tw_lp_load context, for a tw_lpb_load context with tracing off, for equal
+ * tags, n_q == 0 or n_q > TW_MEASURE_MAX_QUANTILES, a q_ppm above 1,000,000 (or
+ * q_ppm NULL), another n, a non-truncated replica over the tw_set_measure_keys
+ * limit and an overfilled bucket table; TW_ERR_OOM for a failed scratch
+ * allocation.  On any failure nothing is written and the context stays usable.
+ * Serves replica contexts in every geometry and traced tw_lpb_load contexts,
+ * tw_set_trace_batch on or off.  A tw_create(devices, n) context gives the
+ * quantiles of the whole batch as if on one device: the latencies stay where
+ * they are, each shard counts digits of the sign-biased values (d ^ 2^63) that
+ * share a rank's prefix so far, and the host picks the digit from the summed
+ * counts, most significant first, starting below the digits that the batch's
+ * min_us and max_us share.  A rank context (tw_create_rank) measures its own
+ * replicas only.  Device scratch for the duration of the call, per shard:
+ * tw_measure's, plus 64 KiB + 12 bytes per replica + 8 bytes per two matching
+ * records, plus 16 * n_q bytes per replica when per_replica is given.
+ * Out of scope: node-partitioned contexts (there is no
+ * tw_lp_measure_quantiles) and a reduction over ranks. */
+#define TW_MEASURE_MAX_QUANTILES 16u
+typedef struct tw_quantile { int64_t lo_us, hi_us; } tw_quantile;
+int tw_measure_quantiles(tw_ctx* ctx, uint32_t tag_from, uint32_t tag_to,
+                         const uint32_t* q_ppm, uint32_t n_q,
+                         tw_quantile* total /* [n_q] or NULL: all pairs of the batch */,
+                         tw_quantile* per_replica /* [n][n_q], replica-major, or NULL */, size_t n,
+                         uint64_t* pairs, uint64_t* truncated /* either may be NULL */);
+/* Device time (ms, HIP events) of the last tw_measure_quantiles by phase: the
+ * join with its emit (tw_measure's kernels: the slowest shard's), the offsets
+ * scan, the per-replica select, the batch-wide digit counts (summed over the
+ * passes, the slowest shard's of each), and the number of those passes.
+ * Writes min(cap, 5) entries and returns how many. */
+int tw_measure_quantiles_ms(tw_ctx* ctx, double* ms, size_t cap);
+
 /* Tie-order audit: run every replica (as tw_run with t_end_us / max_events)
  * under each probe order p in 1..probes (TW_TIE_LIFO, TW_TIE_SCRAMBLE), then
  * under the canonical order, and set tie_flags bit p of every replica whose

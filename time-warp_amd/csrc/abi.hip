@@ -35,6 +35,7 @@
 #include "live_plan.hpp"
 #include "lp_trace_plan.hpp"
 #include "measure_combine.hpp"
+#include "measure_select.hpp"
 #include "shard.hpp"
 #include "tw_dev.hpp"
 
@@ -86,6 +87,11 @@ struct tw_ctx {
     double measure_phase_ms[MEASURE_PHASES] = {};  // ... by kernel (tw_measure_phases_ms): the slowest shard's
     // tw_set_measure_keys, and the testing hook TW_TEST_MEASURE (test_hook_init)
     MeasureCfg measure_cfg{TW_MEASURE_MAX_KEYS, TW_MEASURE_MAX_KEYS, 1024};
+    // tw_measure_quantiles: the per-replica select's LDS-sort capacity (the
+    // testing hook TW_TEST_QUANTILE_LDS lowers it) and the last call's device
+    // time by phase (tw_measure_quantiles_ms)
+    uint32_t quantile_lds = QS_LDS_MAX;
+    double quantile_ms[5] = {};
     uint32_t lp_trace_cap = 0;  // tw_lp_set_trace: records the context keeps track of (each shard holds as many)
 };
 
@@ -115,6 +121,13 @@ void test_hook_init(tw_ctx* c) {
             c->measure_cfg.lds_keys = (uint32_t)lds;
             c->measure_cfg.bucket_keys = (uint32_t)bk;
         }
+    }
+    // TW_TEST_QUANTILE_LDS=n (0 .. 2048) lowers the number of latencies that
+    // tw_measure_quantiles' per-replica select sorts in LDS: a replica of a few
+    // dozen pairs then takes the radix path.
+    if (const char* q = getenv("TW_TEST_QUANTILE_LDS")) {
+        const long n = strtol(q, nullptr, 10);
+        if (n >= 0 && n <= (long)QS_LDS_MAX) c->quantile_lds = (uint32_t)n;
     }
 }
 bool nccl_test_fail(tw_ctx* c) { return c->test_fail_at > 0 && ++c->test_calls == c->test_fail_at; }
@@ -713,6 +726,101 @@ int tw_measure(tw_ctx* c, const tw_measure_spec* spec, tw_measure_out* total, ui
     c->measure_ms = ms;
     std::copy(phase, phase + MEASURE_PHASES, c->measure_phase_ms);
     return TW_OK;
+}
+
+// Every shard joins its replicas with the emit variant, which leaves the pair
+// latencies on its device (MeasureEmit), and selects its own replicas'
+// quantiles.  The batch's are selected over all shards without moving a
+// latency: qs_select (measure_select.hpp) asks every shard for the digit counts
+// of a pass and takes the steps on the sums.  As in tw_measure the caller's
+// buffers are written only when everything succeeded.
+int tw_measure_quantiles(tw_ctx* c, uint32_t tag_from, uint32_t tag_to, const uint32_t* q_ppm, uint32_t n_q,
+                         tw_quantile* total, tw_quantile* per_replica, size_t n, uint64_t* pairs,
+                         uint64_t* truncated) {
+    if (!c) return TW_ERR_INVALID;
+    for (tw_shard* s : c->sh) {
+        int rc = sh_measure_state(s);
+        if (rc) return rc;
+    }
+    if (!quantile_args_ok(tag_from, tag_to, q_ppm, n_q)) return TW_ERR_INVALID;
+    if (n == 0) per_replica = nullptr;
+    if (per_replica && n != local_replicas(c)) return TW_ERR_INVALID;
+    // the join's spec: one bin that is never counted (the emit variant stores
+    // a latency where tw_measure bins it)
+    tw_measure_spec spec{};
+    spec.tag_from = tag_from;
+    spec.tag_to = tag_to;
+    spec.n_bins = 1;
+    spec.bin_us = 1;
+    struct Emits {  // the shards' latency buffers, released on every return path
+        std::vector<MeasureEmit> e;
+        ~Emits() {
+            for (MeasureEmit& m : e) measure_emit_free(&m);
+        }
+    } em;
+    em.e.resize(c->sh.size());
+    tw_measure_out tot;
+    measure_empty(&tot);
+    std::vector<tw_quantile> per(per_replica ? n * n_q : 0);
+    double ph[5] = {};
+    size_t off = 0;
+    for (size_t i = 0; i < c->sh.size(); ++i) {
+        tw_shard* s = c->sh[i];
+        const size_t k = sh_replicas(s);
+        tw_measure_out st;
+        double jms = 0.0, sms = 0.0;
+        int rc = sh_measure(s, &spec, c->measure_cfg, &st, nullptr, nullptr, &jms, nullptr, &em.e[i]);
+        if (rc) return rc;
+        measure_add(&tot, &st);
+        if (per_replica) {
+            if (off > n || k > n - off) return TW_ERR_INVALID;
+            rc = select_replicas(sh_device(s), sh_stream(s), em.e[i], (uint32_t)k, q_ppm, n_q, c->quantile_lds,
+                                 per.data() + off * n_q, &sms);
+            if (rc) return rc;
+        }
+        ph[0] = std::max(ph[0], jms);
+        ph[1] = std::max(ph[1], em.e[i].offsets_ms);
+        ph[2] = std::max(ph[2], sms);
+        off += k;
+    }
+    std::vector<tw_quantile> tq(total ? n_q : 0);
+    if (total && tot.pairs == 0) {
+        for (tw_quantile& q : tq) quantile_empty(&q);
+    } else if (total) {
+        QsRanks ranks;
+        qs_ranks(q_ppm, n_q, tot.pairs, &ranks);
+        int64_t val[QS_MAX_RANKS];
+        int rc = TW_OK;
+        uint32_t passes = 0;
+        auto count = [&](const uint64_t* prefix, uint32_t nk, uint32_t shift, uint64_t* hist) {
+            double slowest = 0.0;
+            for (size_t i = 0; i < c->sh.size() && rc == TW_OK; ++i) {
+                double ms = 0.0;
+                rc = select_count(sh_device(c->sh[i]), sh_stream(c->sh[i]), em.e[i], (uint32_t)sh_replicas(c->sh[i]),
+                                  prefix, nk, shift, hist, &ms);
+                slowest = std::max(slowest, ms);
+            }
+            ph[3] += slowest;
+            return rc == TW_OK;
+        };
+        if (!qs_select(ranks, tot.min_us, tot.max_us, count, val, &passes))
+            return rc ? rc : TW_ERR_STATE;  // (a rank beyond the counted: the buffers disagree with `pairs`)
+        ph[4] = passes;
+        for (uint32_t i = 0; i < n_q; ++i) tq[i] = tw_quantile{val[ranks.lo_at[i]], val[ranks.hi_at[i]]};
+    }
+    if (total) std::copy(tq.begin(), tq.end(), total);
+    if (per_replica) std::copy(per.begin(), per.end(), per_replica);
+    if (pairs) *pairs = tot.pairs;
+    if (truncated) *truncated = tot.truncated;
+    std::copy(ph, ph + 5, c->quantile_ms);
+    return TW_OK;
+}
+
+int tw_measure_quantiles_ms(tw_ctx* c, double* ms, size_t cap) {
+    if (!c || !ms) return TW_ERR_INVALID;
+    const size_t n = cap < 5 ? cap : 5;
+    std::copy(c->quantile_ms, c->quantile_ms + n, ms);
+    return (int)n;
 }
 
 int tw_set_measure_keys(tw_ctx* c, uint32_t max_keys) {

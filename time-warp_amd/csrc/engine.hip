@@ -2065,15 +2065,15 @@ int sh_measure_state(tw_shard* c) {
 }
 
 int sh_measure(tw_shard* c, const tw_measure_spec* spec, const MeasureCfg& cfg, tw_measure_out* total, uint64_t* hist,
-               tw_measure_out* per, double* kernel_ms, double* phase_ms) {
+               tw_measure_out* per, double* kernel_ms, double* phase_ms, MeasureEmit* emit) {
     int rc = sh_measure_state(c);
     if (rc) return rc;
     const Dev& d = c->d;
     if (c->lpm.lpb)  // (one count per replica in trace_n; d.R counts lanes)
         return measure_run(c->device, c->stream, d.trace, d.trace_n, c->lpm.n_rep, d.trace_cap, spec, cfg, total, hist, per,
-                           kernel_ms, phase_ms);
+                           kernel_ms, phase_ms, emit);
     return measure_run(c->device, c->stream, d.trace, d.scal + (size_t)SC_TRACE_N * d.R, d.R, d.trace_cap, spec, cfg,
-                       total, hist, per, kernel_ms, phase_ms);
+                       total, hist, per, kernel_ms, phase_ms, emit);
 }
 
 int sh_last_launch_ms(tw_shard* c, double* out, size_t cap) {

@@ -56,6 +56,12 @@
 // No lane waits for another, every probe loop ends after 2048 steps, every
 // barrier is under a workgroup-uniform condition.
 //
+// tw_measure_quantiles (measure_select.hip) runs the same pass with the two
+// join kernels' EMIT instantiations: a pair's latency is stored into a buffer
+// segmented by replica (tw_measure_offsets: an exclusive scan of m_r / 2 over
+// the replicas, behind the count and the plan) where tw_measure bins it.  The
+// EMIT = false instantiations are what the kernels were before the template.
+//
 // LDS per workgroup: 2048 keys x (8 B val + 8 B t + 1 B flags) = 34 KiB, the
 // histogram 4096 x 4 B = 16 KiB, a few accumulators: ~50.1 KiB static, under
 // the 64 KiB a workgroup may hold; 3 workgroups per CU of the 160 KiB.
@@ -175,12 +181,19 @@ __device__ __forceinline__ bool ms_after(const MsKeys& k, uint32_t i, uint32_t j
     return fi > fj;
 }
 
+// EMIT (tw_measure_quantiles): instead of binning a pair's latency, store it at
+// the replica's segment of qlat -- qoff[r] + its claim on the pairs counter,
+// which the classes already take -- and leave the replica's pairs in qfill[r].
+// A segment holds m / 2 latencies, and a pair is two of the m keys.
+template <bool EMIT>
 __global__ __launch_bounds__(MS_WG) void tw_measure_join(const uint4* __restrict__ trace,
                                                          const uint64_t* __restrict__ emitted, uint32_t R,
                                                          uint32_t tag_from, uint32_t tag_to, uint32_t n_bins,
                                                          int64_t lo_us, int64_t bin_us,
                                                          const uint32_t* __restrict__ cnt, tw_measure_out* total,
-                                                         unsigned long long* hist, tw_measure_out* per) {
+                                                         unsigned long long* hist, tw_measure_out* per,
+                                                         const unsigned long long* __restrict__ qoff,
+                                                         uint32_t* __restrict__ qfill, long long* __restrict__ qlat) {
     __shared__ MsKeys K;
     __shared__ uint32_t s_hist[MS_BINS];
     __shared__ uint32_t s_n;       // gather cursor
@@ -270,13 +283,15 @@ __global__ __launch_bounds__(MS_WG) void tw_measure_join(const uint4* __restrict
                 else if (!has1) cls = 1u;
                 else if (!(K.fl[i + 1] & KF_TO)) cls = 3u;
                 else cls = (i + 2 < m && K.val[i + 2] == v) ? 3u : 0u;
-                atomicAdd(&s_cls[cls], 1u);
+                const uint32_t at = atomicAdd(&s_cls[cls], 1u);
                 if (cls == 0) {
                     const int64_t d = (int64_t)((uint64_t)K.t[i + 1] - (uint64_t)K.t[i]);
                     __hip_atomic_fetch_min(&s_min, (long long)d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     __hip_atomic_fetch_max(&s_max, (long long)d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     atomicAdd(&s_sum, (unsigned long long)d);
-                    if (d < lo_us) {
+                    if (EMIT) {
+                        if (at < (m >> 1)) qlat[qoff[r] + at] = (long long)d;
+                    } else if (d < lo_us) {
                         atomicAdd(&s_uf, 1ull);
                     } else {
                         const uint64_t bin = ((uint64_t)d - (uint64_t)lo_us) / (uint64_t)bin_us;
@@ -292,6 +307,7 @@ __global__ __launch_bounds__(MS_WG) void tw_measure_join(const uint4* __restrict
             o.pairs = s_cls[0]; o.open_from = s_cls[1]; o.open_to = s_cls[2]; o.repeated = s_cls[3];
             o.min_us = s_min; o.max_us = s_max; o.sum_us = (int64_t)s_sum;
             if (per) per[r] = o;
+            if (EMIT) qfill[r] = s_cls[0];  // (a large replica: 0, tw_measure_join_large adds to it)
             wg.pairs += o.pairs; wg.open_from += o.open_from; wg.open_to += o.open_to; wg.repeated += o.repeated;
             wg.min_us = o.min_us < wg.min_us ? o.min_us : wg.min_us;
             wg.max_us = o.max_us > wg.max_us ? o.max_us : wg.max_us;
@@ -462,6 +478,11 @@ __global__ __launch_bounds__(MS_WG) void tw_measure_ranges(const uint32_t* __res
 // slot state: a side's "seen" bit, and its "seen again" bit
 constexpr uint32_t SF_FROM = 1, SF_FROM2 = 2, SF_TO = 4, SF_TO2 = 8;
 
+// EMIT: as tw_measure_join's.  A replica's buckets span workgroups, so its
+// fill count in qfill[r] is the cursor: a wave counts its lanes' pairs of the
+// bucket, its last lane claims that many places with one atomic, and the lanes
+// store behind the claim in a second walk over their slots.
+template <bool EMIT>
 __global__ __launch_bounds__(MS_WG) void tw_measure_join_large(const uint4* __restrict__ keys,
                                                                const uint32_t* __restrict__ bcnt,
                                                                const uint32_t* __restrict__ bstart,
@@ -471,7 +492,10 @@ __global__ __launch_bounds__(MS_WG) void tw_measure_join_large(const uint4* __re
                                                                unsigned long long n_keys, uint32_t n_bins,
                                                                int64_t lo_us, int64_t bin_us, MsPlan* plan,
                                                                tw_measure_out* total, unsigned long long* hist,
-                                                               tw_measure_out* per) {
+                                                               tw_measure_out* per,
+                                                               const unsigned long long* __restrict__ qoff,
+                                                               uint32_t* __restrict__ qfill,
+                                                               long long* __restrict__ qlat) {
     // slot MP_SLOTS is the id MP_EMPTY's own
     __shared__ unsigned long long s_val[MP_SLOTS + 1];
     __shared__ unsigned long long s_acc[MP_SLOTS + 1];
@@ -571,6 +595,7 @@ __global__ __launch_bounds__(MS_WG) void tw_measure_join_large(const uint4* __re
             atomicAdd(&s_acc[s], to ? t : 0ull - t);
         }
         __syncthreads();
+        uint32_t mine = 0;  // EMIT: this lane's pairs of the bucket
         for (uint32_t s = tid; s <= MP_SLOTS; s += MS_WG) {
             const uint32_t st = s_st[s];
             if (!st) continue;
@@ -584,12 +609,38 @@ __global__ __launch_bounds__(MS_WG) void tw_measure_join_large(const uint4* __re
                 __hip_atomic_fetch_min(&s_min, (long long)d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 __hip_atomic_fetch_max(&s_max, (long long)d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 atomicAdd(&s_sum, (unsigned long long)d);
-                if (d < lo_us) {
+                if (EMIT) {
+                    ++mine;
+                } else if (d < lo_us) {
                     atomicAdd(&s_uf, 1ull);
                 } else {
                     const uint64_t bin = ((uint64_t)d - (uint64_t)lo_us) / (uint64_t)bin_us;
                     if (bin >= n_bins) atomicAdd(&s_of, 1ull);
                     else atomicAdd(&s_hist[(uint32_t)bin], 1u);
+                }
+            }
+        }
+        if (EMIT) {
+            // (every lane of the wave is here: the loop above has ended for all
+            // of them; nothing below waits, the shuffles read registers)
+            const uint32_t lane = tid & 63u;
+            uint32_t upto = mine;  // inclusive scan over the wave
+            for (uint32_t o = 1; o < 64; o <<= 1) {
+                const uint32_t v = __shfl_up(upto, o, 64);
+                if (lane >= o) upto += v;
+            }
+            const uint32_t wave_n = __shfl(upto, 63, 64);
+            if (wave_n) {  // (uniform over the wave)
+                uint32_t base = 0;
+                if (lane == 63) base = atomicAdd(&qfill[r], wave_n);
+                base = __shfl(base, 63, 64);
+                uint32_t at = base + upto - mine;
+                const uint32_t room = rep[r].m >> 1;
+                const unsigned long long seg = qoff[r];
+                for (uint32_t s = tid; s <= MP_SLOTS; s += MS_WG) {
+                    if (s_st[s] != (SF_FROM | SF_TO)) continue;
+                    if (at < room) qlat[seg + at] = (long long)s_acc[s];
+                    ++at;
                 }
             }
         }
@@ -617,12 +668,48 @@ __global__ __launch_bounds__(MS_WG) void tw_measure_join_large(const uint4* __re
     }
 }
 
+// EMIT: the replicas' segments of the latency buffer.  Replica r gets m_r / 2
+// places (m_r its matching records: cnt[r], or MsRep::m once the plan marked it
+// large; none when truncated), off[r] the exclusive sum, off[R] the total.  One
+// workgroup: lane i sums a contiguous run of replicas, the 256 sums are scanned
+// in LDS, and the lane walks its run again.
+__global__ __launch_bounds__(MS_WG) void tw_measure_offsets(const uint32_t* __restrict__ cnt,
+                                                            const MsRep* __restrict__ rep, uint32_t R,
+                                                            unsigned long long* __restrict__ off) {
+    __shared__ unsigned long long s_sum[MS_WG];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t run = (R + MS_WG - 1) / MS_WG;
+    const uint32_t r0 = (uint64_t)tid * run < R ? tid * run : R, r1 = R - r0 < run ? R : r0 + run;
+    auto places = [&](uint32_t r) -> unsigned long long {
+        uint32_t m = cnt[r];
+        if (m == MS_TRUNC) return 0;
+        if (m > MS_KEYS) m = rep ? rep[r].m : 0u;
+        return m >> 1;
+    };
+    unsigned long long sum = 0;
+    for (uint32_t r = r0; r < r1; ++r) sum += places(r);
+    s_sum[tid] = sum;
+    __syncthreads();
+    for (uint32_t o = 1; o < MS_WG; o <<= 1) {
+        const unsigned long long v = tid >= o ? s_sum[tid - o] : 0ull;
+        __syncthreads();
+        s_sum[tid] += v;
+        __syncthreads();
+    }
+    unsigned long long at = s_sum[tid] - sum;
+    for (uint32_t r = r0; r < r1; ++r) {
+        off[r] = at;
+        at += places(r);
+    }
+    if (tid == MS_WG - 1) off[R] = s_sum[tid];
+}
+
 // the call's device scratch and events, released on every return path
 struct MsRes {
     void* buf = nullptr;
     void* plan = nullptr;  // partition path: header, per-replica entries, the large list
     void* part = nullptr;  // partition path: per-bucket arrays and the keys
-    hipEvent_t ev[11] = {};  // 0-3: the LDS path's; 4-10: made when the partition path runs
+    hipEvent_t ev[13] = {};  // 0-3: the LDS path's; 4-10: made when the partition path runs; 11-12: emit's
     ~MsRes() {
         if (buf) (void)hipFree(buf);
         if (plan) (void)hipFree(plan);
@@ -647,7 +734,7 @@ namespace tw {
 
 int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64_t* emitted, uint32_t R, uint32_t cap,
                 const tw_measure_spec* spec, const MeasureCfg& cfg, tw_measure_out* total, uint64_t* hist,
-                tw_measure_out* per, double* kernel_ms, double* phase_ms) {
+                tw_measure_out* per, double* kernel_ms, double* phase_ms, MeasureEmit* emit) {
     if (!measure_spec_ok(spec) || !trace || !emitted || cap == 0) return TW_ERR_INVALID;
     if (cfg.lds_keys > MS_KEYS || cfg.max_keys < MS_KEYS || cfg.max_keys > MP_MAX_KEYS || cfg.bucket_keys == 0)
         return TW_ERR_INVALID;
@@ -656,6 +743,7 @@ int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64
         if (total) measure_empty(total);
         if (hist) std::memset(hist, 0, (size_t)spec->n_bins * 8);
         if (kernel_ms) *kernel_ms = 0.0;
+        if (emit) *emit = MeasureEmit{};
         return TW_OK;
     }
     // scratch: err word | total | hist[n_bins] | per[R] (when asked for) | cnt[R]
@@ -728,6 +816,36 @@ int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64
             plan.n_buckets > 0x7FFFFFFFull || plan.n_keys > (unsigned long long)R * cfg.max_keys)
             return TW_ERR_STATE;
     }
+    if (emit) {
+        // the latency segments: off[R + 1] | fill[R], then the buffer itself
+        // once the device has summed the places.  The caller owns both from
+        // here on, whatever this call returns (measure_emit_free)
+        *emit = MeasureEmit{};
+        constexpr size_t digits = (size_t)2 * TW_MEASURE_MAX_QUANTILES * 256;  // (select_count's histogram)
+        if (hipMalloc(&emit->buf, ((size_t)R + 1 + digits) * 8 + (size_t)R * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            return TW_ERR_OOM;
+        }
+        emit->off = (unsigned long long*)emit->buf;
+        emit->digits = emit->off + R + 1;
+        emit->fill = (uint32_t*)(emit->digits + digits);
+        for (int i = 11; i < 13; ++i) MSCHK(hipEventCreate(&res.ev[i]));
+        MSCHK(hipMemsetAsync(emit->fill, 0, (size_t)R * 4, stream));
+        MSCHK(hipEventRecord(res.ev[11], stream));
+        tw_measure_offsets<<<1, MS_WG, 0, stream>>>(d_cnt, d_rep, R, emit->off);
+        MSCHK(hipGetLastError());
+        MSCHK(hipEventRecord(res.ev[12], stream));
+        unsigned long long places = 0;
+        MSCHK(hipMemcpyAsync(&places, emit->off + R, 8, hipMemcpyDeviceToHost, stream));
+        MSCHK(hipStreamSynchronize(stream));
+        // (a place per two matching records, and a matching record is a kept one)
+        if (places > (unsigned long long)R * cap / 2) return TW_ERR_STATE;
+        emit->places = places;
+        if (hipMalloc((void**)&emit->lat, (size_t)(places ? places : 1) * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            return TW_ERR_OOM;
+        }
+    }
     if (plan.n_large) {
         // part scratch: bcnt[2 B] | fill[2 B] | bstart[B] | brep[B] | keys[K] (16 B each, 16-aligned)
         const size_t B = (size_t)plan.n_buckets, K = (size_t)plan.n_keys;
@@ -781,8 +899,14 @@ int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64
     const uint32_t need = (uint32_t)(((uint64_t)R + (1u << 20) - 1) >> 20);
     if (grid < need) grid = need;
     MSCHK(hipEventRecord(res.ev[2], stream));
-    tw_measure_join<<<grid, MS_WG, 0, stream>>>(trace, emitted, R, spec->tag_from, spec->tag_to, spec->n_bins,
-                                                spec->lo_us, spec->bin_us, d_cnt, d_total, d_hist, d_per);
+    if (emit)
+        tw_measure_join<true><<<grid, MS_WG, 0, stream>>>(trace, emitted, R, spec->tag_from, spec->tag_to,
+                                                          spec->n_bins, spec->lo_us, spec->bin_us, d_cnt, d_total,
+                                                          d_hist, d_per, emit->off, emit->fill, emit->lat);
+    else
+        tw_measure_join<false><<<grid, MS_WG, 0, stream>>>(trace, emitted, R, spec->tag_from, spec->tag_to,
+                                                           spec->n_bins, spec->lo_us, spec->bin_us, d_cnt, d_total,
+                                                           d_hist, d_per, nullptr, nullptr, nullptr);
     MSCHK(hipGetLastError());
     MSCHK(hipEventRecord(res.ev[3], stream));
     if (plan.n_large) {
@@ -794,9 +918,14 @@ int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64
         const uint32_t lneed = (uint32_t)(((uint64_t)B + (1u << 20) - 1) >> 20);
         if (lgrid < lneed) lgrid = lneed;
         const uint32_t per_wg = (B + lgrid - 1) / lgrid;
-        tw_measure_join_large<<<lgrid, MS_WG, 0, stream>>>(d_keys, d_bcnt, d_bstart, d_brep, d_rep, B, per_wg,
-                                                           plan.n_keys, spec->n_bins, spec->lo_us, spec->bin_us,
-                                                           (MsPlan*)res.plan, d_total, d_hist, d_per);
+        if (emit)
+            tw_measure_join_large<true><<<lgrid, MS_WG, 0, stream>>>(
+                d_keys, d_bcnt, d_bstart, d_brep, d_rep, B, per_wg, plan.n_keys, spec->n_bins, spec->lo_us,
+                spec->bin_us, (MsPlan*)res.plan, d_total, d_hist, d_per, emit->off, emit->fill, emit->lat);
+        else
+            tw_measure_join_large<false><<<lgrid, MS_WG, 0, stream>>>(
+                d_keys, d_bcnt, d_bstart, d_brep, d_rep, B, per_wg, plan.n_keys, spec->n_bins, spec->lo_us,
+                spec->bin_us, (MsPlan*)res.plan, d_total, d_hist, d_per, nullptr, nullptr, nullptr);
         MSCHK(hipGetLastError());
         MSCHK(hipEventRecord(res.ev[10], stream));
         MSCHK(hipMemcpyAsync(&plan.flags, res.plan, 4, hipMemcpyDeviceToHost, stream));
@@ -831,7 +960,18 @@ int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64
         for (double v : ph) *kernel_ms += v;
     }
     if (phase_ms) std::copy(ph, ph + MEASURE_PHASES, phase_ms);
+    if (emit) {
+        float ms = 0.f;
+        MSCHK(hipEventElapsedTime(&ms, res.ev[11], res.ev[12]));
+        emit->offsets_ms = ms;
+    }
     return TW_OK;
+}
+
+void measure_emit_free(MeasureEmit* e) {
+    if (e->buf) (void)hipFree(e->buf);
+    if (e->lat) (void)hipFree(e->lat);
+    *e = MeasureEmit{};
 }
 
 }  // namespace tw

@@ -75,13 +75,41 @@ struct MeasureCfg {
 // tw_measure's kernels in launch order of their kind: count, plan,
 // part<false>, ranges, part<true>, join, join_large
 constexpr int MEASURE_PHASES = 7;
+// tw_measure_quantiles: the join's emit variant leaves every pair's latency in
+// device memory, segmented by replica -- replica r's are lat[off[r] ..
+// off[r] + fill[r]), its segment of off[r + 1] - off[r] places filled from the
+// front in no particular order.  Made by sh_measure / measure_run when `emit`
+// is given (no histogram is counted then; hist and the under / overflow read
+// 0), owned by the caller whatever they return: measure_emit_free.
+struct MeasureEmit {
+    void* buf = nullptr;               // off[R + 1] | digits[32 x 256] | fill[R]
+    unsigned long long* off = nullptr;
+    unsigned long long* digits = nullptr;  // select_count's device histogram
+    uint32_t* fill = nullptr;
+    long long* lat = nullptr;
+    uint64_t places = 0;               // off[R]
+    double offsets_ms = 0.0;           // device time of the offsets scan
+};
+TW_HIDDEN void measure_emit_free(MeasureEmit* e);
 TW_HIDDEN int sh_measure(tw_shard* c, const tw_measure_spec* spec, const MeasureCfg& cfg, tw_measure_out* total,
-                         uint64_t* hist, tw_measure_out* per, double* kernel_ms, double* phase_ms);
+                         uint64_t* hist, tw_measure_out* per, double* kernel_ms, double* phase_ms,
+                         MeasureEmit* emit = nullptr);
 // the measure pass itself (measure.hip) over a shard's trace buffer
 // ([cap][R][2] quads) and its per-replica emitted counts (R: replicas)
 TW_HIDDEN int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64_t* emitted, uint32_t R,
                           uint32_t cap, const tw_measure_spec* spec, const MeasureCfg& cfg, tw_measure_out* total,
-                          uint64_t* hist, tw_measure_out* per, double* kernel_ms, double* phase_ms);
+                          uint64_t* hist, tw_measure_out* per, double* kernel_ms, double* phase_ms,
+                          MeasureEmit* emit = nullptr);
+// the selects over a MeasureEmit of R replicas (measure_select.hip), blocking:
+// select_replicas writes out[R][n_q] (host), a replica at a time per workgroup
+// -- sorted in LDS up to lds_cap latencies (at most QS_LDS_MAX), radix-selected
+// beyond; select_count adds to hist[n_ranks][256] (host) the digit at `shift`
+// of every latency of the shard whose key matches prefix[j] above it.
+constexpr uint32_t QS_LDS_MAX = 2048;
+TW_HIDDEN int select_replicas(int device, hipStream_t stream, const MeasureEmit& e, uint32_t R, const uint32_t* q_ppm,
+                              uint32_t n_q, uint32_t lds_cap, tw_quantile* out, double* ms);
+TW_HIDDEN int select_count(int device, hipStream_t stream, const MeasureEmit& e, uint32_t R, const uint64_t* prefix,
+                           uint32_t n_ranks, uint32_t shift, uint64_t* hist, double* ms);
 // tw_lp_set_trace ... on one shard of a node-partitioned context: the shard
 // keeps up to cap records of its node block under one counter.
 // sh_lp_trace_state: TW_ERR_STATE nothing loaded / tracing off, TW_ERR_INVALID

@@ -155,4 +155,7 @@ assert RESULT_DTYPE.itemsize == C.sizeof(TwReplicaResult)
 # numpy dtype with the same layout as tw_measure_out (tw_measure's per-replica array)
 MEASURE_DTYPE = _np.dtype([(f, _np.int64 if t is C.c_int64 else _np.uint64) for f, t in TwMeasureOut._fields_])
 assert MEASURE_DTYPE.itemsize == C.sizeof(TwMeasureOut)
+# tw_quantile (tw_measure_quantiles' entries)
+QUANTILE_DTYPE = _np.dtype([("lo_us", _np.int64), ("hi_us", _np.int64)])
+MEASURE_MAX_QUANTILES = 16   # TW_MEASURE_MAX_QUANTILES
 assert isa.ABI_VERSION == 4

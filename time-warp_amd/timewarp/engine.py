@@ -16,7 +16,7 @@ from typing import Optional
 
 import numpy as np
 
-from .abi import (MEASURE_DTYPE, RESULT_DTYPE, TwLiveDelays, TwLpState, TwMeasureOut, TwMeasureSpec, TwStats,
+from .abi import (MEASURE_DTYPE, QUANTILE_DTYPE, RESULT_DTYPE, TwLiveDelays, TwLpState, TwMeasureOut, TwMeasureSpec, TwStats,
                   TwTableDraw)
 from .scenario import Scenario
 
@@ -34,7 +34,8 @@ EXPORTS = ["tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_ru
            "tw_draw_link_table", "tw_lpb_batch", "tw_measure", "tw_measure_ms", "tw_set_sweep", "tw_sweep_stats",
            "tw_set_prefix", "tw_prefix_stats", "tw_set_measure_keys", "tw_measure_phases_ms",
            "tw_prefix_clean_stats", "tw_set_trace_batch", "tw_lp_set_trace", "tw_lp_read_trace", "tw_lp_measure",
-           "tw_set_live_delays", "tw_live_stats", "tw_sweep_path_stats"]
+           "tw_set_live_delays", "tw_live_stats", "tw_sweep_path_stats", "tw_measure_quantiles",
+           "tw_measure_quantiles_ms"]
 GEOMETRIES = ("dense", "sparse", "half", "wave", "lp", "narrow", "lpb", "compact")  # TW_GEO_* order
 
 # tw_trace_rec (include/timewarp.h)
@@ -118,6 +119,11 @@ def load_library(path: Optional[str] = None):
     lib.tw_measure_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.tw_set_measure_keys.argtypes = [C.c_void_p, C.c_uint32]
     lib.tw_measure_phases_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    if hasattr(lib, "tw_measure_quantiles"):
+        lib.tw_measure_quantiles.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        lib.tw_measure_quantiles_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.tw_measure_quantiles.restype = lib.tw_measure_quantiles_ms.restype = C.c_int
     lib.tw_set_sweep.argtypes = [C.c_void_p, C.c_int]
     lib.tw_sweep_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
     lib.tw_set_prefix.argtypes = [C.c_void_p, C.c_int]
@@ -525,6 +531,38 @@ class Engine:
         _check(self.lib.tw_measure(self.ctx, C.byref(spec), C.byref(tot), hist.ctypes.data if hist.size else None,
                                    per.ctypes.data if n else None, n), "tw_measure")
         return {f: int(getattr(tot, f)) for f, _ in TwMeasureOut._fields_}, hist, per
+
+    def measure_quantiles(self, tag_from: int, tag_to: int, q_ppm=(500000,), per_replica: bool = False):
+        """Exact order statistics of the latency t(tag_to) - t(tag_from) over
+        measure()'s pairs, selected on the GPU (tw_measure_quantiles).  q_ppm:
+        up to 16 quantiles in parts per million.  Returns (total, per_replica,
+        pairs, truncated): `total` a QUANTILE_DTYPE array with one (lo_us,
+        hi_us) per quantile over all pairs of the batch -- with n pairs sorted
+        ascending and pos = q * (n - 1), lo is the value at pos div 10^6 and hi
+        the next one when pos mod 10^6 != 0, so the median is (lo + hi) / 2 at
+        500000; (INT64_MAX, INT64_MIN) without pairs -- and per_replica the
+        same per replica, shape [replicas][len(q_ppm)] (or None).  Statuses
+        and contexts as measure()."""
+        q = np.ascontiguousarray([int(x) if 0 <= int(x) < 1 << 32 else (1 << 32) - 1 for x in q_ppm], np.uint32)
+        tot = np.zeros(q.size, QUANTILE_DTYPE)
+        n = self.scn.n_replicas if (per_replica and self.scn is not None) else 0
+        per = np.zeros((n, q.size), QUANTILE_DTYPE) if per_replica else None
+        pairs, trunc = C.c_uint64(), C.c_uint64()
+        _check(self.lib.tw_measure_quantiles(self.ctx, int(tag_from), int(tag_to), q.ctypes.data if q.size else None,
+                                             q.size, tot.ctypes.data if q.size else None,
+                                             per.ctypes.data if n and q.size else None, n, C.byref(pairs),
+                                             C.byref(trunc)), "tw_measure_quantiles")
+        return tot, per, int(pairs.value), int(trunc.value)
+
+    QUANTILE_PHASES = ("join_emit", "offsets", "select_replicas", "select_total", "total_passes")
+
+    def measure_quantiles_ms(self) -> dict:
+        """Device time (ms) of the last measure_quantiles() by phase (the
+        slowest shard's of each), and the batch-wide select's pass count."""
+        buf = np.zeros(len(self.QUANTILE_PHASES), np.float64)
+        n = self.lib.tw_measure_quantiles_ms(self.ctx, buf.ctypes.data, buf.shape[0])
+        _check(n, "tw_measure_quantiles_ms")
+        return dict(zip(self.QUANTILE_PHASES[:n], buf[:n].tolist()))
 
     def set_measure_keys(self, max_keys: int) -> "Engine":
         """The matching records one non-truncated replica may hold in measure()

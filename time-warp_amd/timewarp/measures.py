@@ -142,6 +142,44 @@ def measure_reference(per_replica_records, emitted, cap: int, spec: dict):
     return total, np.array(hist, dtype=np.uint64), per
 
 
+def quantile_of_sorted(d, q_ppm: int):
+    """(lo, hi) of tw_measure_quantiles for the ascending list `d`: with
+    pos = q_ppm * (len(d) - 1), lo = d[pos div 10^6] and hi = d[pos div 10^6 +
+    (pos mod 10^6 != 0)]; (INT64_MAX, INT64_MIN) for an empty list."""
+    if not 0 <= int(q_ppm) <= 1_000_000:
+        raise ValueError("q_ppm must be in 0 .. 1,000,000")
+    if not d:
+        return _I64_MAX, _I64_MIN
+    i, rem = divmod(int(q_ppm) * (len(d) - 1), 1_000_000)
+    return d[i], d[i + (1 if rem else 0)]
+
+
+def quantile_reference(per_replica_records, emitted, cap: int, tag_from: int, tag_to: int, q_ppm):
+    """tw_measure_quantiles restated on the host, from pair_latencies and
+    Python's sorted.  Arguments as measure_reference's, q_ppm a sequence of
+    parts per million.  Returns (total, per_replica, pairs, truncated): total a
+    list of (lo_us, hi_us) per quantile over all pairs of the batch,
+    per_replica an int64 array [replicas][len(q_ppm)][2]; a truncated replica
+    contributes to `truncated` alone and its entries are the empty one."""
+    import numpy as np
+
+    q_ppm = [int(q) for q in q_ppm]
+    per = np.zeros((len(per_replica_records), len(q_ppm), 2), np.int64)
+    every, pairs, truncated = [], 0, 0
+    for r, recs in enumerate(per_replica_records):
+        lat = []
+        if int(emitted[r]) > cap:
+            truncated += 1
+        else:
+            lat = sorted(pair_latencies(list(recs)[:int(emitted[r])], int(tag_from), int(tag_to))[0])
+        pairs += len(lat)
+        every += lat
+        for i, q in enumerate(q_ppm):
+            per[r, i] = quantile_of_sorted(lat, q)
+    every.sort()
+    return [quantile_of_sorted(every, q) for q in q_ppm], per, pairs, truncated
+
+
 def first_receipts(records, tag: int, lo_us: int = 0, bin_us: int = 1000, n_bins: int = 16):
     """The first-receipt distribution of `tag` (gossip's TAG_RUMOR_FIRST: the
     propagation curve) from canonical records -- LPEngine.lp_trace's, an

@@ -19,8 +19,14 @@ written or read x 16 B; a model, not a counter).  The reference bench's own
 message count: --senders 256 --msgs 1000 --replicas 256 --geometry lpb
 --max-keys 524288 --host-sample 2.
 
+--quantiles adds Engine.measure_quantiles on the same run: p50 / p99 / p99.9 of
+the round trip, batch-wide and per replica, with the call's device time by phase
+(the join with its emit, the offsets scan, the per-replica select, the
+batch-wide digit passes) beside tw_measure's; the sampled replicas' entries and,
+when the whole batch is sampled, the total must equal quantile_reference.
+
 usage: python tools/measure_probe.py [--senders 8] [--msgs 40] [--replicas 65536] [--geometry lpb]
-                                     [--trace-batch] [--max-keys N] [--host-sample 256]
+                                     [--trace-batch] [--max-keys N] [--host-sample 256] [--quantiles]
                                      [--out profiles/measure/probe.log]"""
 import argparse
 import os
@@ -33,7 +39,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "time-warp_amd"))
 from timewarp import scenarios  # noqa: E402
 from timewarp.engine import Engine, draw_link_table  # noqa: E402
-from timewarp.measures import measure_reference, measures_from_trace, trace_tuples  # noqa: E402
+from timewarp.measures import measure_reference, measures_from_trace, quantile_reference, trace_tuples  # noqa: E402
 from timewarp.scenarios import TAG_PING_SENT, TAG_PONG  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -45,6 +51,7 @@ ap.add_argument("--max-keys", type=int, default=0, help="Engine.set_measure_keys
 ap.add_argument("--geometry", default=None, help="Engine.load's geometry (default: the library's choice)")
 ap.add_argument("--trace-batch", action="store_true",
                 help="lpb: the traced run with Engine.set_trace_batch on (tw_lp_batch<true> records the due runs)")
+ap.add_argument("--quantiles", action="store_true", help="also Engine.measure_quantiles: p50 / p99 / p99.9")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "measure", "probe.log"))
 a = ap.parse_args()
 if a.trace_batch and a.geometry != "lpb":
@@ -113,6 +120,32 @@ with Engine(0) as e:
     say(f"tw_measure without per_replica: wall {(time.perf_counter() - t0) * 1e3:.2f} ms, "
         f"kernels {e.measure_ms():.3f} ms")
     say(f"total {total}")
+    if a.quantiles:
+        qs = (500000, 990000, 999000)
+
+        def say_quantiles(what, wall):
+            ph = e.measure_quantiles_ms()
+            dev = ph["join_emit"] + ph["offsets"] + ph["select_replicas"] + ph["select_total"]
+            say(f"tw_measure_quantiles {what}: wall {wall:.2f} ms, device {dev:.3f} ms = join with emit "
+                f"{ph['join_emit']:.3f} + offsets {ph['offsets']:.3f} + per-replica select {ph['select_replicas']:.3f} + "
+                f"batch select {ph['select_total']:.3f} ({int(ph['total_passes'])} digit passes)")
+
+        for i in range(3):
+            t0 = time.perf_counter()
+            qtot, qper, qpairs, qtrunc = e.measure_quantiles(spec["tag_from"], spec["tag_to"], qs, per_replica=True)
+            say_quantiles(f"call {i}", (time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        qtot2, _, _, _ = e.measure_quantiles(spec["tag_from"], spec["tag_to"], qs)
+        say_quantiles("without per_replica", (time.perf_counter() - t0) * 1e3)
+        assert qtot2.tobytes() == qtot.tobytes() and (qpairs, qtrunc) == (total["pairs"], total["truncated"])
+        for q, v in zip(qs, qtot):
+            say(f"  p{q / 1e4:g}: lo {int(v['lo_us'])} us, hi {int(v['hi_us'])} us")
+        # the histogram brackets every quantile's bin
+        edges = np.concatenate([[0], np.cumsum(hist)])
+        for q, v in zip(qs, qtot):
+            b = (int(v["lo_us"]) - spec["lo_us"]) // spec["bin_us"]
+            if total["underflow"] == 0 and 0 <= b < spec["n_bins"]:
+                assert edges[b] <= q * (qpairs - 1) // 1000000 < edges[b + 1], (q, b)
     say(f"hist[{spec['lo_us']} + i * {spec['bin_us']} us] {hist.tolist()}")
     assert total["pairs"] == S * M * R and total["truncated"] == 0, total
 
@@ -140,6 +173,13 @@ with Engine(0) as e:
     assert int(per["sum_us"][sample].sum()) == rtot["sum_us"]
     say(f"device per_replica entries of the {n} sampled replicas equal measure_reference: "
         f"pairs {rtot['pairs']}, min {rtot['min_us']}, max {rtot['max_us']}, sum {rtot['sum_us']}")
+    if a.quantiles:
+        wtot, wper, _, _ = quantile_reference(recs, emitted, cap, spec["tag_from"], spec["tag_to"], qs)
+        assert np.array_equal(qper["lo_us"][sample], wper[:, :, 0]) and np.array_equal(qper["hi_us"][sample], wper[:, :, 1])
+        if n == R:
+            assert qtot.tolist() == [tuple(x) for x in wtot]
+        say(f"device per-replica quantiles of the {n} sampled replicas equal quantile_reference"
+            + ("; so does the batch's" if n == R else ""))
 
 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
 with open(a.out, "w") as f:
