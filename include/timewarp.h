@@ -565,6 +565,99 @@ int tw_measure_quantiles(tw_ctx* ctx, uint32_t tag_from, uint32_t tag_to,
  * Writes min(cap, 5) entries and returns how many. */
 int tw_measure_quantiles_ms(tw_ctx* ctx, double* ms, size_t cap);
 
+/* Time series over virtual time, binned on the device: how many TRACE records
+ * of a tag fall into each bin (EVENTS), when each node first traced the tag
+ * (FIRST: a propagation curve, timewarp.measures.first_receipts), and a
+ * latency's count / sum / min / max by the time its pair opened (LATENCY).
+ *
+ * A replica's records are tw_measure's kept records; a replica that emitted
+ * more than the trace cap adds 1 to `truncated` and contributes nothing else.
+ * The items, each with a time:
+ *   TW_SERIES_EVENTS   every kept record whose tag is `tag`, at its t;
+ *   TW_SERIES_FIRST    every (replica, node) with at least one such record, at
+ *                      the earliest such record's t (several records at that
+ *                      time still count once);
+ *   TW_SERIES_LATENCY  every pair of tw_measure(tag, tag_to) -- the same id
+ *                      classes, key limits (tw_set_measure_keys) and statuses
+ *                      for an overfull replica or bucket -- at its t_from;
+ *                      stat[i] folds the latencies d = t_to - t_from of the
+ *                      pairs of bin i, and `counted` is tw_measure's `pairs`.
+ * An item with time t is an `underflow` when t < t0_us; otherwise it belongs to
+ * bin i = (t - t0_us) / bin_us, or is an `overflow` when i >= n_bins (compared
+ * first, subtracted afterwards: with t0_us >= 0 nothing wraps).  count[i] is
+ * the number of items in bin i, and sum(count) + underflow + overflow ==
+ * counted, for the batch and for every replica.  Everything is integer: the
+ * results do not depend on the geometry, the shard count or the order of the
+ * device's atomics.
+ *
+ * total: the batch; count: n_bins counters; stat: n_bins entries, LATENCY only
+ * (must be NULL otherwise); per_replica: n entries in replica order;
+ * per_replica_count: [n][n_bins], replica-major (LATENCY: pair counts); each
+ * may be NULL.  n = 0, or the context's replica count.  There is no per-replica
+ * stat.
+ * Blocking, stream-ordered after the last tw_run; changes no state and may be
+ * called repeatedly and between calls of tw_measure.  Contexts and statuses as
+ * tw_measure's (tw_lp_measure's for tw_lp_measure_series; each call answers the
+ * other kind of context with TW_ERR_INVALID): TW_ERR_STATE when nothing is
+ * loaded or tracing is off; TW_ERR_INVALID for a bad spec (a mode that does not
+ * exist, n_bins == 0 or above the mode's maximum, t0_us < 0, bin_us < 1,
+ * reserved != 0, LATENCY with tag_to == tag, another mode with tag_to != 0),
+ * for stat outside LATENCY, for another n, for FIRST over a scenario of more
+ * than 2^25 nodes, and where tw_measure refuses a replica's keys or a bucket;
+ * TW_ERR_OOM for failed device scratch.  On any failure nothing is written and
+ * the context stays usable.  A tw_create(devices, n) context runs every shard
+ * and adds the shards' outputs on the host; a rank context measures its own
+ * replicas only.
+ * FIRST keeps a table of first times per (replica, node) in device scratch,
+ * 8 bytes an entry, at most 2^25 entries (256 MiB) at a time: the replicas are
+ * processed in chunks of that many entries.
+ * tw_lp_measure_series, for a tw_lp_load context with tw_lp_set_trace on:
+ * EVENTS and FIRST are binned by every shard over its own node block and added
+ * on the host (no record moves); LATENCY gathers the records onto the first
+ * device as tw_lp_measure does, and like it refuses a rank of a larger job.  A
+ * truncated context (more records emitted than the cap, over all shards) gives
+ * truncated == 1 and nothing else. */
+enum { TW_SERIES_EVENTS = 0, TW_SERIES_FIRST = 1, TW_SERIES_LATENCY = 2 };
+#define TW_SERIES_MAX_BINS      8192u   /* EVENTS, FIRST */
+#define TW_SERIES_MAX_LAT_BINS  1024u   /* LATENCY */
+
+typedef struct tw_series_spec {
+    uint32_t tag;       /* the TRACE immediate whose records are binned; LATENCY: tag_from */
+    uint32_t tag_to;    /* LATENCY: the closing tag, != tag; other modes: must be 0 */
+    uint32_t mode;      /* TW_SERIES_* */
+    uint32_t n_bins;    /* 1 .. the mode's maximum */
+    int64_t  t0_us;     /* start of bin 0, >= 0 */
+    int64_t  bin_us;    /* bin width, >= 1 */
+    uint64_t reserved;  /* 0 */
+} tw_series_spec;
+
+typedef struct tw_series_out {
+    uint64_t counted;    /* items with a time: in a bin, or in underflow / overflow */
+    uint64_t underflow;  /* time < t0_us */
+    uint64_t overflow;   /* (time - t0_us) / bin_us >= n_bins */
+    uint64_t truncated;  /* replicas that emitted more than the trace cap: nothing else from them */
+    int64_t  t_min, t_max;  /* over the counted times; INT64_MAX / INT64_MIN when counted == 0 */
+} tw_series_out;
+
+typedef struct tw_series_stat {  /* LATENCY: the pairs whose t_from falls in the bin */
+    int64_t sum_us;              /* two's-complement sum of d */
+    int64_t min_us, max_us;      /* INT64_MAX / INT64_MIN for an empty bin */
+} tw_series_stat;
+
+int tw_measure_series(tw_ctx* ctx, const tw_series_spec* spec, tw_series_out* total,
+                      uint64_t* count /* [n_bins] or NULL */,
+                      tw_series_stat* stat /* [n_bins] or NULL; must be NULL unless LATENCY */,
+                      tw_series_out* per_replica /* [n] or NULL */,
+                      uint64_t* per_replica_count /* [n][n_bins], replica-major, or NULL */, size_t n);
+int tw_lp_measure_series(tw_ctx* ctx, const tw_series_spec* spec, tw_series_out* total,
+                         uint64_t* count, tw_series_stat* stat);
+/* Device time (ms, HIP events) of the last tw_measure_series or
+ * tw_lp_measure_series by phase, the slowest shard's of each: the join with its
+ * emit (LATENCY), FIRST's table fill, the binning (EVENTS' count kernel, FIRST's
+ * pass over the table), the latency fold.  0 for phases that did not run.
+ * Writes min(cap, 4) entries and returns how many. */
+int tw_measure_series_ms(tw_ctx* ctx, double* ms, size_t cap);
+
 /* Tie-order audit: run every replica (as tw_run with t_end_us / max_events)
  * under each probe order p in 1..probes (TW_TIE_LIFO, TW_TIE_SCRAMBLE), then
  * under the canonical order, and set tie_flags bit p of every replica whose

@@ -36,6 +36,7 @@
 #include "lp_trace_plan.hpp"
 #include "measure_combine.hpp"
 #include "measure_select.hpp"
+#include "measure_series.hpp"
 #include "shard.hpp"
 #include "tw_dev.hpp"
 
@@ -92,6 +93,11 @@ struct tw_ctx {
     // time by phase (tw_measure_quantiles_ms)
     uint32_t quantile_lds = QS_LDS_MAX;
     double quantile_ms[5] = {};
+    // tw_measure_series: FIRST's table entries at a time (the testing hook
+    // TW_TEST_SERIES lowers it) and the last call's device time by phase
+    // (tw_measure_series_ms)
+    uint64_t series_entries = SERIES_MAX_ENTRIES;
+    double series_ms[SERIES_PHASES] = {};
     uint32_t lp_trace_cap = 0;  // tw_lp_set_trace: records the context keeps track of (each shard holds as many)
 };
 
@@ -128,6 +134,13 @@ void test_hook_init(tw_ctx* c) {
     if (const char* q = getenv("TW_TEST_QUANTILE_LDS")) {
         const long n = strtol(q, nullptr, 10);
         if (n >= 0 && n <= (long)QS_LDS_MAX) c->quantile_lds = (uint32_t)n;
+    }
+    // TW_TEST_SERIES=entries (1 .. 2^25) lowers the (replica, node) entries that
+    // tw_measure_series' FIRST mode tables at a time: a few dozen replicas then
+    // take several chunks.
+    if (const char* s = getenv("TW_TEST_SERIES")) {
+        const long long n = strtoll(s, nullptr, 10);
+        if (n >= 1 && n <= (long long)SERIES_MAX_ENTRIES) c->series_entries = (uint64_t)n;
     }
 }
 bool nccl_test_fail(tw_ctx* c) { return c->test_fail_at > 0 && ++c->test_calls == c->test_fail_at; }
@@ -823,6 +836,63 @@ int tw_measure_quantiles_ms(tw_ctx* c, double* ms, size_t cap) {
     return (int)n;
 }
 
+// Every shard bins its own replicas; the host folds the shards' outputs
+// (measure_series.hpp) into temporaries handed out only when every shard
+// succeeded.  The phase times are the slowest shard's of each phase.
+int tw_measure_series(tw_ctx* c, const tw_series_spec* spec, tw_series_out* total, uint64_t* count,
+                      tw_series_stat* stat, tw_series_out* per_replica, uint64_t* per_replica_count, size_t n) {
+    if (!c || !spec) return TW_ERR_INVALID;
+    for (tw_shard* s : c->sh) {
+        int rc = sh_measure_state(s);
+        if (rc) return rc;
+    }
+    if (!series_spec_ok(spec)) return TW_ERR_INVALID;
+    if (stat && spec->mode != TW_SERIES_LATENCY) return TW_ERR_INVALID;
+    if (n == 0) per_replica = nullptr, per_replica_count = nullptr;
+    if ((per_replica || per_replica_count) && n != local_replicas(c)) return TW_ERR_INVALID;
+    const uint32_t nb = spec->n_bins;
+    tw_series_out tot;
+    series_empty(&tot);
+    std::vector<uint64_t> cnt(nb, 0), sh_cnt(nb);
+    std::vector<tw_series_stat> st(stat ? nb : 0), sh_st(stat ? nb : 0);
+    for (tw_series_stat& s : st) series_stat_empty(&s);
+    std::vector<tw_series_out> per(per_replica ? n : 0), sh_per;
+    std::vector<uint64_t> rows(per_replica_count ? n * nb : 0), sh_rows;
+    double ph[SERIES_PHASES] = {}, sph[SERIES_PHASES];
+    size_t off = 0;
+    for (tw_shard* s : c->sh) {
+        const size_t k = sh_replicas(s);
+        tw_series_out sh_tot;
+        if (per_replica) sh_per.resize(k);
+        if (per_replica_count) sh_rows.resize(k * nb);
+        int rc = sh_measure_series(s, spec, c->measure_cfg, c->series_entries, &sh_tot, sh_cnt.data(),
+                                   stat ? sh_st.data() : nullptr, per_replica ? sh_per.data() : nullptr,
+                                   per_replica_count ? sh_rows.data() : nullptr, sph);
+        if (rc) return rc;
+        if (!series_combine(&tot, cnt.data(), stat ? st.data() : nullptr, nb, per_replica ? per.data() : nullptr,
+                            per_replica_count ? rows.data() : nullptr, n, &sh_tot, sh_cnt.data(),
+                            stat ? sh_st.data() : nullptr, per_replica ? sh_per.data() : nullptr,
+                            per_replica_count ? sh_rows.data() : nullptr, off, k))
+            return TW_ERR_INVALID;
+        for (int i = 0; i < SERIES_PHASES; ++i) ph[i] = std::max(ph[i], sph[i]);
+        off += k;
+    }
+    if (total) *total = tot;
+    if (count) std::memcpy(count, cnt.data(), (size_t)nb * 8);
+    if (stat) std::memcpy(stat, st.data(), (size_t)nb * sizeof(tw_series_stat));
+    if (per_replica) std::memcpy(per_replica, per.data(), n * sizeof(tw_series_out));
+    if (per_replica_count) std::memcpy(per_replica_count, rows.data(), n * nb * 8);
+    std::copy(ph, ph + SERIES_PHASES, c->series_ms);
+    return TW_OK;
+}
+
+int tw_measure_series_ms(tw_ctx* c, double* ms, size_t cap) {
+    if (!c || !ms) return TW_ERR_INVALID;
+    const size_t n = cap < (size_t)SERIES_PHASES ? cap : (size_t)SERIES_PHASES;
+    std::copy(c->series_ms, c->series_ms + n, ms);
+    return (int)n;
+}
+
 int tw_set_measure_keys(tw_ctx* c, uint32_t max_keys) {
     if (!c || max_keys < TW_MEASURE_MAX_KEYS || max_keys > TW_MEASURE_MAX_KEYS_LARGE) return TW_ERR_INVALID;
     c->measure_cfg.max_keys = max_keys;  // (of the context: every shard's tw_measure gets it)
@@ -1143,6 +1213,40 @@ int lp_trace_counts(tw_ctx* c, std::vector<uint64_t>& counts) {
     }
     return TW_OK;
 }
+
+// The shards' kept records of a context that is not truncated (p.emitted of
+// them, > 0), gathered into one buffer on shard 0's device by copies ordered on
+// shard 0's stream, with the one replica's emitted count behind them.  The
+// caller synchronises that stream before the buffer goes.
+struct LpGather {
+    void* p = nullptr;
+    uint64_t* d_n = nullptr;
+    ~LpGather() {
+        if (p) (void)hipFree(p);
+    }
+};
+int lp_gather(tw_ctx* c, const LpTracePlan& p, LpGather* buf) {
+    const int dev0 = c->dev[0];
+    hipStream_t st = sh_stream(c->sh[0]);
+    HIPCHK_A(hipSetDevice(dev0));
+    // the records, then the replica's emitted count
+    if (hipMalloc(&buf->p, (size_t)p.emitted * 32 + 8) != hipSuccess) {
+        (void)hipGetLastError();  // (not sticky: the context stays usable)
+        return TW_ERR_OOM;
+    }
+    for (size_t i = 0; i < c->sh.size(); ++i) {
+        if (!p.kept[i]) continue;
+        char* dst = (char*)buf->p + (size_t)p.off[i] * 32;
+        const size_t bytes = (size_t)p.kept[i] * 32;
+        if (c->dev[i] == dev0)
+            HIPCHK_A(hipMemcpyAsync(dst, sh_lp_trace_dev(c->sh[i]), bytes, hipMemcpyDeviceToDevice, st));
+        else
+            HIPCHK_A(hipMemcpyPeerAsync(dst, dev0, sh_lp_trace_dev(c->sh[i]), c->dev[i], bytes, st));
+    }
+    buf->d_n = (uint64_t*)((char*)buf->p + (size_t)p.emitted * 32);
+    HIPCHK_A(hipMemcpyAsync(buf->d_n, &p.emitted, 8, hipMemcpyHostToDevice, st));
+    return TW_OK;
+}
 }  // namespace
 
 int tw_lp_read_trace(tw_ctx* c, tw_trace_rec* out, size_t cap, uint64_t* n_emitted) {
@@ -1196,33 +1300,13 @@ int tw_lp_measure(tw_ctx* c, const tw_measure_spec* spec, tw_measure_out* out, u
     if (p.truncated) {
         tot.truncated = 1;  // (contributes nothing else; no gather)
     } else if (p.emitted) {
-        struct Buf {
-            void* p = nullptr;
-            ~Buf() {
-                if (p) (void)hipFree(p);
-            }
-        } buf;
+        LpGather buf;
+        rc = lp_gather(c, p, &buf);
+        if (rc) return rc;
         const int dev0 = c->dev[0];
         hipStream_t st = sh_stream(c->sh[0]);
-        HIPCHK_A(hipSetDevice(dev0));
-        // the records, then the replica's emitted count
-        if (hipMalloc(&buf.p, (size_t)p.emitted * 32 + 8) != hipSuccess) {
-            (void)hipGetLastError();  // (not sticky: the context stays usable)
-            return TW_ERR_OOM;
-        }
-        for (size_t i = 0; i < c->sh.size(); ++i) {
-            if (!p.kept[i]) continue;
-            char* dst = (char*)buf.p + (size_t)p.off[i] * 32;
-            const size_t bytes = (size_t)p.kept[i] * 32;
-            if (c->dev[i] == dev0)
-                HIPCHK_A(hipMemcpyAsync(dst, sh_lp_trace_dev(c->sh[i]), bytes, hipMemcpyDeviceToDevice, st));
-            else
-                HIPCHK_A(hipMemcpyPeerAsync(dst, dev0, sh_lp_trace_dev(c->sh[i]), c->dev[i], bytes, st));
-        }
-        uint64_t* d_n = (uint64_t*)((char*)buf.p + (size_t)p.emitted * 32);
-        HIPCHK_A(hipMemcpyAsync(d_n, &p.emitted, 8, hipMemcpyHostToDevice, st));
-        rc = measure_run(dev0, st, (const uint4*)buf.p, d_n, 1, (uint32_t)p.emitted, spec, c->measure_cfg, &tot, h.data(),
-                         nullptr, &ms, phase);
+        rc = measure_run(dev0, st, (const uint4*)buf.p, buf.d_n, 1, (uint32_t)p.emitted, spec, c->measure_cfg, &tot,
+                         h.data(), nullptr, &ms, phase);
         HIPCHK_A(hipStreamSynchronize(st));  // (before the buffer goes)
         if (rc) return rc;
     }
@@ -1230,6 +1314,61 @@ int tw_lp_measure(tw_ctx* c, const tw_measure_spec* spec, tw_measure_out* out, u
     if (hist) std::memcpy(hist, h.data(), (size_t)spec->n_bins * 8);
     c->measure_ms = ms;
     std::copy(phase, phase + MEASURE_PHASES, c->measure_phase_ms);
+    return TW_OK;
+}
+
+// EVENTS and FIRST: every shard bins the records of its own node block (the
+// blocks are disjoint, so a node's first time is one shard's) and the host adds
+// the outputs: no gather, no merge.  LATENCY: a pair may span shards, so the
+// records are gathered as for tw_lp_measure and binned on the first device.
+int tw_lp_measure_series(tw_ctx* c, const tw_series_spec* spec, tw_series_out* total, uint64_t* count,
+                         tw_series_stat* stat) {
+    if (!c || !spec) return TW_ERR_INVALID;
+    for (tw_shard* s : c->sh) {
+        int rc = sh_lp_trace_state(s);
+        if (rc) return rc;
+    }
+    if (!series_spec_ok(spec)) return TW_ERR_INVALID;
+    const bool is_lat = spec->mode == TW_SERIES_LATENCY;
+    if (stat && !is_lat) return TW_ERR_INVALID;
+    if (is_lat && c->world != (int)c->sh.size()) return TW_ERR_INVALID;  // a rank of a larger job: no job-wide gather
+    std::vector<uint64_t> counts;
+    int rc = lp_trace_counts(c, counts);
+    if (rc) return rc;
+    const LpTracePlan p = lp_trace_plan(counts.data(), counts.size(), c->lp_trace_cap);
+    const uint32_t nb = spec->n_bins;
+    tw_series_out tot;
+    series_empty(&tot);
+    std::vector<uint64_t> cnt(nb, 0), sh_cnt(nb);
+    std::vector<tw_series_stat> st(stat ? nb : 0);
+    for (tw_series_stat& s : st) series_stat_empty(&s);
+    double ph[SERIES_PHASES] = {}, sph[SERIES_PHASES];
+    if (p.truncated) {
+        tot.truncated = 1;  // (contributes nothing else)
+    } else if (is_lat && p.emitted) {
+        LpGather buf;
+        rc = lp_gather(c, p, &buf);
+        if (rc) return rc;
+        hipStream_t s0 = sh_stream(c->sh[0]);
+        rc = series_run(c->dev[0], s0, (const uint4*)buf.p, buf.d_n, 1, (uint32_t)p.emitted, 1u /* no table: not FIRST */,
+                        c->series_entries, spec, c->measure_cfg, &tot, cnt.data(), stat ? st.data() : nullptr, nullptr,
+                        nullptr, ph);
+        HIPCHK_A(hipStreamSynchronize(s0));  // (before the buffer goes)
+        if (rc) return rc;
+    } else if (!is_lat) {
+        for (tw_shard* s : c->sh) {
+            tw_series_out sh_tot;
+            rc = sh_lp_measure_series(s, spec, c->measure_cfg, c->series_entries, &sh_tot, sh_cnt.data(), sph);
+            if (rc) return rc;
+            series_combine(&tot, cnt.data(), nullptr, nb, nullptr, nullptr, 0, &sh_tot, sh_cnt.data(), nullptr, nullptr,
+                           nullptr, 0, 0);
+            for (int i = 0; i < SERIES_PHASES; ++i) ph[i] = std::max(ph[i], sph[i]);
+        }
+    }
+    if (total) *total = tot;
+    if (count) std::memcpy(count, cnt.data(), (size_t)nb * 8);
+    if (stat) std::memcpy(stat, st.data(), (size_t)nb * sizeof(tw_series_stat));
+    std::copy(ph, ph + SERIES_PHASES, c->series_ms);
     return TW_OK;
 }
 

@@ -2076,6 +2076,31 @@ int sh_measure(tw_shard* c, const tw_measure_spec* spec, const MeasureCfg& cfg, 
                        total, hist, per, kernel_ms, phase_ms, emit);
 }
 
+int sh_measure_series(tw_shard* c, const tw_series_spec* spec, const MeasureCfg& cfg, uint64_t max_entries,
+                      tw_series_out* total, uint64_t* count, tw_series_stat* stat, tw_series_out* per,
+                      uint64_t* per_count, double* phase_ms) {
+    int rc = sh_measure_state(c);
+    if (rc) return rc;
+    const Dev& d = c->d;
+    // (FIRST's table: a record's node is one of the scenario's, d.Ntot of them per replica)
+    if (c->lpm.lpb)
+        return series_run(c->device, c->stream, d.trace, d.trace_n, c->lpm.n_rep, d.trace_cap, d.Ntot, max_entries, spec,
+                          cfg, total, count, stat, per, per_count, phase_ms);
+    return series_run(c->device, c->stream, d.trace, d.scal + (size_t)SC_TRACE_N * d.R, d.R, d.trace_cap, d.Ntot,
+                      max_entries, spec, cfg, total, count, stat, per, per_count, phase_ms);
+}
+
+int sh_lp_measure_series(tw_shard* c, const tw_series_spec* spec, const MeasureCfg& cfg, uint64_t max_entries,
+                         tw_series_out* total, uint64_t* count, double* phase_ms) {
+    int rc = sh_lp_trace_state(c);
+    if (rc) return rc;
+    const Dev& d = c->d;
+    // one replica; the records carry the scenario's node numbers, so the table
+    // spans all of them although only this shard's block occurs
+    return series_run(c->device, c->stream, d.trace, d.trace_n, 1, d.trace_cap, d.Ntot, max_entries, spec, cfg, total,
+                      count, nullptr, nullptr, nullptr, phase_ms);
+}
+
 int sh_last_launch_ms(tw_shard* c, double* out, size_t cap) {
     if (!c || !out) return TW_ERR_INVALID;
     const std::vector<double>& ms = c->times.ms;

@@ -60,7 +60,8 @@
 // join kernels' EMIT instantiations: a pair's latency is stored into a buffer
 // segmented by replica (tw_measure_offsets: an exclusive scan of m_r / 2 over
 // the replicas, behind the count and the plan) where tw_measure bins it.  The
-// EMIT = false instantiations are what the kernels were before the template.
+// ME_BIN instantiations are what the kernels were before the template; ME_TIMES
+// (tw_measure_series' LATENCY mode, measure_series.hip) stores t_from as well.
 //
 // LDS per workgroup: 2048 keys x (8 B val + 8 B t + 1 B flags) = 34 KiB, the
 // histogram 4096 x 4 B = 16 KiB, a few accumulators: ~50.1 KiB static, under
@@ -185,7 +186,11 @@ __device__ __forceinline__ bool ms_after(const MsKeys& k, uint32_t i, uint32_t j
 // the replica's segment of qlat -- qoff[r] + its claim on the pairs counter,
 // which the classes already take -- and leave the replica's pairs in qfill[r].
 // A segment holds m / 2 latencies, and a pair is two of the m keys.
-template <bool EMIT>
+// EMIT is one of three states (tw_measure_series' LATENCY mode takes the third):
+// ME_TIMES stores as ME_LAT does and also the pair's t_from, at the same place
+// of the segment in a second buffer, qtf.
+constexpr int ME_BIN = 0, ME_LAT = 1, ME_TIMES = 2;
+template <int EMIT>
 __global__ __launch_bounds__(MS_WG) void tw_measure_join(const uint4* __restrict__ trace,
                                                          const uint64_t* __restrict__ emitted, uint32_t R,
                                                          uint32_t tag_from, uint32_t tag_to, uint32_t n_bins,
@@ -193,7 +198,8 @@ __global__ __launch_bounds__(MS_WG) void tw_measure_join(const uint4* __restrict
                                                          const uint32_t* __restrict__ cnt, tw_measure_out* total,
                                                          unsigned long long* hist, tw_measure_out* per,
                                                          const unsigned long long* __restrict__ qoff,
-                                                         uint32_t* __restrict__ qfill, long long* __restrict__ qlat) {
+                                                         uint32_t* __restrict__ qfill, long long* __restrict__ qlat,
+                                                         long long* __restrict__ qtf) {
     __shared__ MsKeys K;
     __shared__ uint32_t s_hist[MS_BINS];
     __shared__ uint32_t s_n;       // gather cursor
@@ -290,7 +296,10 @@ __global__ __launch_bounds__(MS_WG) void tw_measure_join(const uint4* __restrict
                     __hip_atomic_fetch_max(&s_max, (long long)d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     atomicAdd(&s_sum, (unsigned long long)d);
                     if (EMIT) {
-                        if (at < (m >> 1)) qlat[qoff[r] + at] = (long long)d;
+                        if (at < (m >> 1)) {
+                            qlat[qoff[r] + at] = (long long)d;
+                            if constexpr (EMIT == ME_TIMES) qtf[qoff[r] + at] = (long long)K.t[i];
+                        }
                     } else if (d < lo_us) {
                         atomicAdd(&s_uf, 1ull);
                     } else {
@@ -481,8 +490,10 @@ constexpr uint32_t SF_FROM = 1, SF_FROM2 = 2, SF_TO = 4, SF_TO2 = 8;
 // EMIT: as tw_measure_join's.  A replica's buckets span workgroups, so its
 // fill count in qfill[r] is the cursor: a wave counts its lanes' pairs of the
 // bucket, its last lane claims that many places with one atomic, and the lanes
-// store behind the claim in a second walk over their slots.
-template <bool EMIT>
+// store behind the claim in a second walk over their slots.  ME_TIMES: a slot
+// also keeps the t of its tag_from key (one key writes it when the id is a
+// pair), in the LDS the histogram leaves free: that state bins nothing.
+template <int EMIT>
 __global__ __launch_bounds__(MS_WG) void tw_measure_join_large(const uint4* __restrict__ keys,
                                                                const uint32_t* __restrict__ bcnt,
                                                                const uint32_t* __restrict__ bstart,
@@ -495,12 +506,14 @@ __global__ __launch_bounds__(MS_WG) void tw_measure_join_large(const uint4* __re
                                                                tw_measure_out* per,
                                                                const unsigned long long* __restrict__ qoff,
                                                                uint32_t* __restrict__ qfill,
-                                                               long long* __restrict__ qlat) {
+                                                               long long* __restrict__ qlat,
+                                                               long long* __restrict__ qtf) {
     // slot MP_SLOTS is the id MP_EMPTY's own
     __shared__ unsigned long long s_val[MP_SLOTS + 1];
     __shared__ unsigned long long s_acc[MP_SLOTS + 1];
     __shared__ uint32_t s_st[MP_SLOTS + 1];
-    __shared__ uint32_t s_hist[MS_BINS];
+    __shared__ uint32_t s_hist[EMIT == ME_TIMES ? 2 : MS_BINS];  // (ME_TIMES: the host passes n_bins = 1)
+    __shared__ unsigned long long s_tf[EMIT == ME_TIMES ? MP_SLOTS + 1 : 1];
     __shared__ uint32_t s_cls[4];  // the current replica's pairs, open_from, open_to, repeated (of this workgroup's buckets)
     __shared__ long long s_min, s_max;
     __shared__ unsigned long long s_sum;
@@ -593,6 +606,8 @@ __global__ __launch_bounds__(MS_WG) void tw_measure_join_large(const uint4* __re
             const uint32_t once = to ? SF_TO : SF_FROM;
             if (atomicOr(&s_st[s], once) & once) atomicOr(&s_st[s], once << 1);
             atomicAdd(&s_acc[s], to ? t : 0ull - t);
+            if constexpr (EMIT == ME_TIMES)
+                if (!to) s_tf[s] = t;  // (a pair has one tag_from key: no other lane writes this slot)
         }
         __syncthreads();
         uint32_t mine = 0;  // EMIT: this lane's pairs of the bucket
@@ -639,7 +654,10 @@ __global__ __launch_bounds__(MS_WG) void tw_measure_join_large(const uint4* __re
                 const unsigned long long seg = qoff[r];
                 for (uint32_t s = tid; s <= MP_SLOTS; s += MS_WG) {
                     if (s_st[s] != (SF_FROM | SF_TO)) continue;
-                    if (at < room) qlat[seg + at] = (long long)s_acc[s];
+                    if (at < room) {
+                        qlat[seg + at] = (long long)s_acc[s];
+                        if constexpr (EMIT == ME_TIMES) qtf[seg + at] = (long long)s_tf[s];
+                    }
                     ++at;
                 }
             }
@@ -820,7 +838,9 @@ int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64
         // the latency segments: off[R + 1] | fill[R], then the buffer itself
         // once the device has summed the places.  The caller owns both from
         // here on, whatever this call returns (measure_emit_free)
+        const bool with_t = emit->with_t;
         *emit = MeasureEmit{};
+        emit->with_t = with_t;
         constexpr size_t digits = (size_t)2 * TW_MEASURE_MAX_QUANTILES * 256;  // (select_count's histogram)
         if (hipMalloc(&emit->buf, ((size_t)R + 1 + digits) * 8 + (size_t)R * 4) != hipSuccess) {
             (void)hipGetLastError();
@@ -841,10 +861,12 @@ int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64
         // (a place per two matching records, and a matching record is a kept one)
         if (places > (unsigned long long)R * cap / 2) return TW_ERR_STATE;
         emit->places = places;
-        if (hipMalloc((void**)&emit->lat, (size_t)(places ? places : 1) * 8) != hipSuccess) {
+        // (with_t: the t_from buffer behind the latencies, place for place)
+        if (hipMalloc((void**)&emit->lat, (size_t)(places ? places : 1) * (with_t ? 16 : 8)) != hipSuccess) {
             (void)hipGetLastError();
             return TW_ERR_OOM;
         }
+        if (with_t) emit->tfrom = emit->lat + (places ? places : 1);
     }
     if (plan.n_large) {
         // part scratch: bcnt[2 B] | fill[2 B] | bstart[B] | brep[B] | keys[K] (16 B each, 16-aligned)
@@ -899,14 +921,19 @@ int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64
     const uint32_t need = (uint32_t)(((uint64_t)R + (1u << 20) - 1) >> 20);
     if (grid < need) grid = need;
     MSCHK(hipEventRecord(res.ev[2], stream));
-    if (emit)
-        tw_measure_join<true><<<grid, MS_WG, 0, stream>>>(trace, emitted, R, spec->tag_from, spec->tag_to,
-                                                          spec->n_bins, spec->lo_us, spec->bin_us, d_cnt, d_total,
-                                                          d_hist, d_per, emit->off, emit->fill, emit->lat);
+    if (emit && emit->with_t)
+        tw_measure_join<ME_TIMES><<<grid, MS_WG, 0, stream>>>(trace, emitted, R, spec->tag_from, spec->tag_to,
+                                                              spec->n_bins, spec->lo_us, spec->bin_us, d_cnt, d_total,
+                                                              d_hist, d_per, emit->off, emit->fill, emit->lat,
+                                                              emit->tfrom);
+    else if (emit)
+        tw_measure_join<ME_LAT><<<grid, MS_WG, 0, stream>>>(trace, emitted, R, spec->tag_from, spec->tag_to,
+                                                            spec->n_bins, spec->lo_us, spec->bin_us, d_cnt, d_total,
+                                                            d_hist, d_per, emit->off, emit->fill, emit->lat, nullptr);
     else
-        tw_measure_join<false><<<grid, MS_WG, 0, stream>>>(trace, emitted, R, spec->tag_from, spec->tag_to,
-                                                           spec->n_bins, spec->lo_us, spec->bin_us, d_cnt, d_total,
-                                                           d_hist, d_per, nullptr, nullptr, nullptr);
+        tw_measure_join<ME_BIN><<<grid, MS_WG, 0, stream>>>(trace, emitted, R, spec->tag_from, spec->tag_to,
+                                                            spec->n_bins, spec->lo_us, spec->bin_us, d_cnt, d_total,
+                                                            d_hist, d_per, nullptr, nullptr, nullptr, nullptr);
     MSCHK(hipGetLastError());
     MSCHK(hipEventRecord(res.ev[3], stream));
     if (plan.n_large) {
@@ -918,14 +945,18 @@ int measure_run(int device, hipStream_t stream, const uint4* trace, const uint64
         const uint32_t lneed = (uint32_t)(((uint64_t)B + (1u << 20) - 1) >> 20);
         if (lgrid < lneed) lgrid = lneed;
         const uint32_t per_wg = (B + lgrid - 1) / lgrid;
-        if (emit)
-            tw_measure_join_large<true><<<lgrid, MS_WG, 0, stream>>>(
+        if (emit && emit->with_t)
+            tw_measure_join_large<ME_TIMES><<<lgrid, MS_WG, 0, stream>>>(
+                d_keys, d_bcnt, d_bstart, d_brep, d_rep, B, per_wg, plan.n_keys, 1u, spec->lo_us, spec->bin_us,
+                (MsPlan*)res.plan, d_total, d_hist, d_per, emit->off, emit->fill, emit->lat, emit->tfrom);
+        else if (emit)
+            tw_measure_join_large<ME_LAT><<<lgrid, MS_WG, 0, stream>>>(
                 d_keys, d_bcnt, d_bstart, d_brep, d_rep, B, per_wg, plan.n_keys, spec->n_bins, spec->lo_us,
-                spec->bin_us, (MsPlan*)res.plan, d_total, d_hist, d_per, emit->off, emit->fill, emit->lat);
+                spec->bin_us, (MsPlan*)res.plan, d_total, d_hist, d_per, emit->off, emit->fill, emit->lat, nullptr);
         else
-            tw_measure_join_large<false><<<lgrid, MS_WG, 0, stream>>>(
+            tw_measure_join_large<ME_BIN><<<lgrid, MS_WG, 0, stream>>>(
                 d_keys, d_bcnt, d_bstart, d_brep, d_rep, B, per_wg, plan.n_keys, spec->n_bins, spec->lo_us,
-                spec->bin_us, (MsPlan*)res.plan, d_total, d_hist, d_per, nullptr, nullptr, nullptr);
+                spec->bin_us, (MsPlan*)res.plan, d_total, d_hist, d_per, nullptr, nullptr, nullptr, nullptr);
         MSCHK(hipGetLastError());
         MSCHK(hipEventRecord(res.ev[10], stream));
         MSCHK(hipMemcpyAsync(&plan.flags, res.plan, 4, hipMemcpyDeviceToHost, stream));

@@ -87,6 +87,11 @@ struct MeasureEmit {
     unsigned long long* digits = nullptr;  // select_count's device histogram
     uint32_t* fill = nullptr;
     long long* lat = nullptr;
+    // tw_measure_series' LATENCY mode sets with_t before the call: every pair's
+    // t_from is then stored as well, at its latency's place (tfrom: the second
+    // half of lat's allocation)
+    bool with_t = false;
+    long long* tfrom = nullptr;
     uint64_t places = 0;               // off[R]
     double offsets_ms = 0.0;           // device time of the offsets scan
 };
@@ -110,6 +115,23 @@ TW_HIDDEN int select_replicas(int device, hipStream_t stream, const MeasureEmit&
                               uint32_t n_q, uint32_t lds_cap, tw_quantile* out, double* ms);
 TW_HIDDEN int select_count(int device, hipStream_t stream, const MeasureEmit& e, uint32_t R, const uint64_t* prefix,
                            uint32_t n_ranks, uint32_t shift, uint64_t* hist, double* ms);
+// tw_measure_series on one shard (measure_series.hip): the states of
+// sh_measure_state; outputs (any may be NULL: total, count[n_bins],
+// stat[n_bins], per[sh_replicas], per_count[sh_replicas][n_bins]) and the
+// device time by phase (SERIES_PHASES entries, measure_series.hpp) written only
+// on success.  max_entries: FIRST's table entries at a time (0: the limit).
+// sh_lp_measure_series: EVENTS / FIRST over the node block of one shard of a
+// traced node-partitioned context, its one replica (states: sh_lp_trace_state).
+// series_run is the pass itself over a trace buffer, as measure_run.
+TW_HIDDEN int sh_measure_series(tw_shard* c, const tw_series_spec* spec, const MeasureCfg& cfg, uint64_t max_entries,
+                                tw_series_out* total, uint64_t* count, tw_series_stat* stat, tw_series_out* per,
+                                uint64_t* per_count, double* phase_ms);
+TW_HIDDEN int sh_lp_measure_series(tw_shard* c, const tw_series_spec* spec, const MeasureCfg& cfg, uint64_t max_entries,
+                                   tw_series_out* total, uint64_t* count, double* phase_ms);
+TW_HIDDEN int series_run(int device, hipStream_t stream, const uint4* trace, const uint64_t* emitted, uint32_t R,
+                         uint32_t cap, uint32_t n_nodes, uint64_t max_entries, const tw_series_spec* spec,
+                         const MeasureCfg& cfg, tw_series_out* total, uint64_t* count, tw_series_stat* stat,
+                         tw_series_out* per, uint64_t* per_count, double* phase_ms);
 // tw_lp_set_trace ... on one shard of a node-partitioned context: the shard
 // keeps up to cap records of its node block under one counter.
 // sh_lp_trace_state: TW_ERR_STATE nothing loaded / tracing off, TW_ERR_INVALID

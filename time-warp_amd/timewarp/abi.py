@@ -136,6 +136,45 @@ class TwMeasureOut(C.Structure):
     ]
 
 
+class TwSeriesSpec(C.Structure):
+    """tw_series_spec: what tw_measure_series bins, and the bins."""
+    _fields_ = [
+        ("tag", C.c_uint32),
+        ("tag_to", C.c_uint32),
+        ("mode", C.c_uint32),
+        ("n_bins", C.c_uint32),
+        ("t0_us", C.c_int64),
+        ("bin_us", C.c_int64),
+        ("reserved", C.c_uint64),
+    ]
+
+
+class TwSeriesOut(C.Structure):
+    """tw_series_out: the items of a series, counted."""
+    _fields_ = [
+        ("counted", C.c_uint64),
+        ("underflow", C.c_uint64),
+        ("overflow", C.c_uint64),
+        ("truncated", C.c_uint64),
+        ("t_min", C.c_int64),
+        ("t_max", C.c_int64),
+    ]
+
+
+class TwSeriesStat(C.Structure):
+    """tw_series_stat: the latencies of one bin's pairs (TW_SERIES_LATENCY)."""
+    _fields_ = [
+        ("sum_us", C.c_int64),
+        ("min_us", C.c_int64),
+        ("max_us", C.c_int64),
+    ]
+
+
+SERIES_EVENTS, SERIES_FIRST, SERIES_LATENCY = 0, 1, 2   # TW_SERIES_*
+SERIES_MODES = {"events": SERIES_EVENTS, "first": SERIES_FIRST, "latency": SERIES_LATENCY}
+SERIES_MAX_BINS = 8192       # TW_SERIES_MAX_BINS (events, first)
+SERIES_MAX_LAT_BINS = 1024   # TW_SERIES_MAX_LAT_BINS (latency)
+
 MEASURE_MAX_KEYS = 2048   # TW_MEASURE_MAX_KEYS
 MEASURE_MAX_KEYS_LARGE = 4194304   # TW_MEASURE_MAX_KEYS_LARGE (tw_set_measure_keys)
 MEASURE_MAX_BINS = 4096   # TW_MEASURE_MAX_BINS
@@ -158,4 +197,8 @@ assert MEASURE_DTYPE.itemsize == C.sizeof(TwMeasureOut)
 # tw_quantile (tw_measure_quantiles' entries)
 QUANTILE_DTYPE = _np.dtype([("lo_us", _np.int64), ("hi_us", _np.int64)])
 MEASURE_MAX_QUANTILES = 16   # TW_MEASURE_MAX_QUANTILES
+# tw_series_out / tw_series_stat (tw_measure_series' arrays)
+SERIES_DTYPE = _np.dtype([(f, _np.int64 if t is C.c_int64 else _np.uint64) for f, t in TwSeriesOut._fields_])
+SERIES_STAT_DTYPE = _np.dtype([(f, _np.int64) for f, _ in TwSeriesStat._fields_])
+assert SERIES_DTYPE.itemsize == C.sizeof(TwSeriesOut) and SERIES_STAT_DTYPE.itemsize == C.sizeof(TwSeriesStat)
 assert isa.ABI_VERSION == 4

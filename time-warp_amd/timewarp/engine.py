@@ -16,8 +16,9 @@ from typing import Optional
 
 import numpy as np
 
-from .abi import (MEASURE_DTYPE, QUANTILE_DTYPE, RESULT_DTYPE, TwLiveDelays, TwLpState, TwMeasureOut, TwMeasureSpec, TwStats,
-                  TwTableDraw)
+from .abi import (MEASURE_DTYPE, QUANTILE_DTYPE, RESULT_DTYPE, SERIES_DTYPE, SERIES_LATENCY, SERIES_MODES,
+                  SERIES_STAT_DTYPE, TwLiveDelays, TwLpState, TwMeasureOut, TwMeasureSpec, TwSeriesOut, TwSeriesSpec,
+                  TwStats, TwTableDraw)
 from .scenario import Scenario
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,7 +36,7 @@ EXPORTS = ["tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_ru
            "tw_set_prefix", "tw_prefix_stats", "tw_set_measure_keys", "tw_measure_phases_ms",
            "tw_prefix_clean_stats", "tw_set_trace_batch", "tw_lp_set_trace", "tw_lp_read_trace", "tw_lp_measure",
            "tw_set_live_delays", "tw_live_stats", "tw_sweep_path_stats", "tw_measure_quantiles",
-           "tw_measure_quantiles_ms"]
+           "tw_measure_quantiles_ms", "tw_measure_series", "tw_lp_measure_series", "tw_measure_series_ms"]
 GEOMETRIES = ("dense", "sparse", "half", "wave", "lp", "narrow", "lpb", "compact")  # TW_GEO_* order
 
 # tw_trace_rec (include/timewarp.h)
@@ -124,6 +125,14 @@ def load_library(path: Optional[str] = None):
                                              C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         lib.tw_measure_quantiles_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         lib.tw_measure_quantiles.restype = lib.tw_measure_quantiles_ms.restype = C.c_int
+    if hasattr(lib, "tw_measure_series"):  # (an older in-tree build under TW_LIB lacks them)
+        lib.tw_measure_series.argtypes = [C.c_void_p, C.POINTER(TwSeriesSpec), C.POINTER(TwSeriesOut), C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.tw_lp_measure_series.argtypes = [C.c_void_p, C.POINTER(TwSeriesSpec), C.POINTER(TwSeriesOut), C.c_void_p,
+                                             C.c_void_p]
+        lib.tw_measure_series_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        for name in ("tw_measure_series", "tw_lp_measure_series", "tw_measure_series_ms"):
+            getattr(lib, name).restype = C.c_int
     lib.tw_set_sweep.argtypes = [C.c_void_p, C.c_int]
     lib.tw_sweep_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
     lib.tw_set_prefix.argtypes = [C.c_void_p, C.c_int]
@@ -563,6 +572,69 @@ class Engine:
         n = self.lib.tw_measure_quantiles_ms(self.ctx, buf.ctypes.data, buf.shape[0])
         _check(n, "tw_measure_quantiles_ms")
         return dict(zip(self.QUANTILE_PHASES[:n], buf[:n].tolist()))
+
+    @staticmethod
+    def _series_spec(tag, t0_us, bin_us, n_bins, mode, tag_to) -> TwSeriesSpec:
+        m = SERIES_MODES.get(mode, mode) if isinstance(mode, str) else mode
+        if isinstance(m, str):
+            raise ValueError(f"mode must be one of {sorted(SERIES_MODES)}")
+        return TwSeriesSpec(tag=int(tag), tag_to=int(tag_to), mode=int(m), n_bins=int(n_bins), t0_us=int(t0_us),
+                            bin_us=int(bin_us), reserved=0)
+
+    def measure_series(self, tag: int, t0_us: int, bin_us: int, n_bins: int, mode: str = "events", tag_to: int = 0,
+                       per_replica: bool = False):
+        """TRACE records over virtual time, binned on the GPU
+        (tw_measure_series) into bins [t0_us + i * bin_us, t0_us + (i + 1) *
+        bin_us).  mode "events": every kept record of `tag` at its time;
+        "first": every (replica, node) that traced `tag`, at its earliest such
+        record (measures.first_receipts: a propagation curve); "latency": every
+        pair of measure(tag, tag_to) at its t_from.  Returns (total, count,
+        stat, per_replica, per_replica_count): `total` a dict of
+        tw_series_out's fields, `count` the n_bins uint64 item counts, `stat` a
+        SERIES_STAT_DTYPE array with the sum / min / max of the latencies of
+        each bin's pairs ("latency", otherwise None), per_replica a
+        SERIES_DTYPE array in replica order and per_replica_count uint64
+        [replicas][n_bins] (both None unless per_replica).  Contexts and
+        statuses as measure()."""
+        spec = self._series_spec(tag, t0_us, bin_us, n_bins, mode, tag_to)
+        nb = max(int(n_bins), 0)
+        tot = TwSeriesOut()
+        count = np.zeros(nb, np.uint64)
+        stat = np.zeros(nb, SERIES_STAT_DTYPE) if spec.mode == SERIES_LATENCY else None
+        n = self.scn.n_replicas if (per_replica and self.scn is not None) else 0
+        per = np.zeros(n, SERIES_DTYPE) if per_replica else None
+        rows = np.zeros((n, nb), np.uint64) if per_replica else None
+        _check(self.lib.tw_measure_series(self.ctx, C.byref(spec), C.byref(tot), count.ctypes.data if nb else None,
+                                          stat.ctypes.data if stat is not None and nb else None,
+                                          per.ctypes.data if n else None, rows.ctypes.data if n and nb else None, n),
+               "tw_measure_series")
+        return {f: int(getattr(tot, f)) for f, _ in TwSeriesOut._fields_}, count, stat, per, rows
+
+    SERIES_PHASES = ("join_emit", "first_fill", "bin", "latency_fold")
+
+    def measure_series_ms(self) -> dict:
+        """Device time (ms) of the last measure_series() or lp_measure_series()
+        by phase (the slowest shard's of each; 0 for phases that did not run)."""
+        buf = np.zeros(len(self.SERIES_PHASES), np.float64)
+        n = self.lib.tw_measure_series_ms(self.ctx, buf.ctypes.data, buf.shape[0])
+        _check(n, "tw_measure_series_ms")
+        return dict(zip(self.SERIES_PHASES[:n], buf[:n].tolist()))
+
+    def lp_measure_series(self, tag: int, t0_us: int, bin_us: int, n_bins: int, mode: str = "events", tag_to: int = 0):
+        """measure_series() over a node-partitioned context's one replica
+        (tw_lp_measure_series): (total, count, stat).  "events" and "first" are
+        binned by every device over its own nodes and added on the host;
+        "latency" joins the records of all devices as lp_measure() does.  A
+        truncated context gives truncated == 1 and nothing else."""
+        spec = self._series_spec(tag, t0_us, bin_us, n_bins, mode, tag_to)
+        nb = max(int(n_bins), 0)
+        tot = TwSeriesOut()
+        count = np.zeros(nb, np.uint64)
+        stat = np.zeros(nb, SERIES_STAT_DTYPE) if spec.mode == SERIES_LATENCY else None
+        _check(self.lib.tw_lp_measure_series(self.ctx, C.byref(spec), C.byref(tot), count.ctypes.data if nb else None,
+                                             stat.ctypes.data if stat is not None and nb else None),
+               "tw_lp_measure_series")
+        return {f: int(getattr(tot, f)) for f, _ in TwSeriesOut._fields_}, count, stat
 
     def set_measure_keys(self, max_keys: int) -> "Engine":
         """The matching records one non-truncated replica may hold in measure()

@@ -180,6 +180,74 @@ def quantile_reference(per_replica_records, emitted, cap: int, tag_from: int, ta
     return [quantile_of_sorted(every, q) for q in q_ppm], per, pairs, truncated
 
 
+def series_reference(per_replica_records, emitted, cap: int, spec: dict):
+    """tw_measure_series restated on the host, in plain Python over tuples.
+    per_replica_records, emitted, cap: as measure_reference's; spec: {"tag",
+    "tag_to" (latency), "mode" ("events", "first" or "latency"), "t0_us",
+    "bin_us", "n_bins"}.  Returns (total dict, count uint64[n_bins], stat
+    (n_bins, 3) int64 of (sum_us, min_us, max_us) for "latency" else None,
+    per-replica SERIES_DTYPE array, per-replica counts uint64
+    [replicas][n_bins])."""
+    import numpy as np
+
+    from .abi import SERIES_DTYPE
+
+    mode, tag, tag_to = spec.get("mode", "events"), int(spec["tag"]), int(spec.get("tag_to", 0))
+    t0, width, n_bins = int(spec.get("t0_us", 0)), int(spec.get("bin_us", 1)), int(spec.get("n_bins", 1))
+    if mode not in ("events", "first", "latency"):
+        raise ValueError("mode must be events, first or latency")
+    if mode == "latency" and tag == tag_to:
+        raise ValueError("tag and tag_to must differ")
+    if n_bins < 1 or width < 1 or t0 < 0:
+        raise ValueError("n_bins and bin_us must be >= 1, t0_us >= 0")
+    n = len(per_replica_records)
+    per = np.zeros(n, SERIES_DTYPE)
+    rows = np.zeros((n, n_bins), np.uint64)
+    sums, mins, maxs = [0] * n_bins, [_I64_MAX] * n_bins, [_I64_MIN] * n_bins
+    for r, recs in enumerate(per_replica_records):
+        per[r]["t_min"], per[r]["t_max"] = _I64_MAX, _I64_MIN
+        if int(emitted[r]) > cap:
+            per[r]["truncated"] = 1
+            continue
+        kept = [(int(t), int(node), int(k), int(v)) for t, node, k, v in list(recs)[:int(emitted[r])]]
+        if mode == "events":
+            items = [(t, None) for t, _node, k, _v in kept if k == tag]
+        elif mode == "first":
+            first: Dict[int, int] = {}
+            for t, node, k, _v in kept:
+                if k == tag and (node not in first or t < first[node]):
+                    first[node] = t
+            items = [(t, None) for t in first.values()]
+        else:
+            # pair_latencies' pairs, each with the time of its tag_from record
+            sides: Dict[int, Tuple[list, list]] = {}
+            for t, _node, k, v in kept:
+                if k in (tag, tag_to):
+                    sides.setdefault(v, ([], []))[k == tag_to].append(t)
+            items = [(tf[0], _wrap64(tt[0] - tf[0])) for _v, (tf, tt) in sorted(sides.items())
+                     if len(tf) == 1 and len(tt) == 1]
+            assert [d for _t, d in items] == pair_latencies(kept, tag, tag_to)[0]   # (both ascend by id)
+        for t, d in items:
+            per[r]["counted"] += 1
+            per[r]["t_min"], per[r]["t_max"] = min(int(per[r]["t_min"]), t), max(int(per[r]["t_max"]), t)
+            if t < t0:
+                per[r]["underflow"] += 1
+            elif (t - t0) // width >= n_bins:
+                per[r]["overflow"] += 1
+            else:
+                b = (t - t0) // width
+                rows[r, b] += 1
+                if d is not None:
+                    sums[b], mins[b], maxs[b] = sums[b] + d, min(mins[b], d), max(maxs[b], d)
+    total = {f: int(per[f].sum()) for f in ("counted", "underflow", "overflow", "truncated")}
+    total["t_min"] = int(per["t_min"].min()) if n else _I64_MAX
+    total["t_max"] = int(per["t_max"].max()) if n else _I64_MIN
+    stat = None
+    if mode == "latency":
+        stat = np.array([[_wrap64(s) for s in sums], mins, maxs], dtype=np.int64).T.copy()
+    return total, rows.sum(axis=0, dtype=np.uint64), stat, per, rows
+
+
 def first_receipts(records, tag: int, lo_us: int = 0, bin_us: int = 1000, n_bins: int = 16):
     """The first-receipt distribution of `tag` (gossip's TAG_RUMOR_FIRST: the
     propagation curve) from canonical records -- LPEngine.lp_trace's, an

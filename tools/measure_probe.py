@@ -25,8 +25,21 @@ the round trip, batch-wide and per replica, with the call's device time by phase
 batch-wide digit passes) beside tw_measure's; the sampled replicas' entries and,
 when the whole batch is sampled, the total must equal quantile_reference.
 
+--series adds Engine.measure_series on the same run: the Pong curve (events),
+the senders' first Pongs (first) and the round trip by send time (latency: the
+mean and the largest latency of every send-time bin, which is where a hotspot's
+growing backlog shows), each with the call's device time by phase; the sampled
+replicas' per-replica entries and rows must equal series_reference.
+
+--config gossip [--nodes 1048576] [--shards 1] is another run altogether: a
+traced node-partitioned gossip run (LPEngine, lp_set_trace), whose propagation
+curve -- every node's first receipt, TAG_RUMOR_FIRST -- is binned on the device
+(LPEngine.lp_measure_series) and, on the same run, by the host path it replaces:
+lp_trace() plus measures.first_receipts.  The two curves must be equal.
+
 usage: python tools/measure_probe.py [--senders 8] [--msgs 40] [--replicas 65536] [--geometry lpb]
                                      [--trace-batch] [--max-keys N] [--host-sample 256] [--quantiles]
+                                     [--series] [--config gossip [--nodes N] [--shards K]]
                                      [--out profiles/measure/probe.log]"""
 import argparse
 import os
@@ -38,9 +51,10 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "time-warp_amd"))
 from timewarp import scenarios  # noqa: E402
-from timewarp.engine import Engine, draw_link_table  # noqa: E402
-from timewarp.measures import measure_reference, measures_from_trace, quantile_reference, trace_tuples  # noqa: E402
-from timewarp.scenarios import TAG_PING_SENT, TAG_PONG  # noqa: E402
+from timewarp.engine import Engine, LPEngine, draw_link_table, lp_scenario  # noqa: E402
+from timewarp.measures import (first_receipts, measure_reference, measures_from_trace, quantile_reference,  # noqa: E402
+                               series_reference, trace_tuples)
+from timewarp.scenarios import TAG_PING_SENT, TAG_PONG, TAG_RUMOR_FIRST  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--senders", type=int, default=8)
@@ -52,6 +66,12 @@ ap.add_argument("--geometry", default=None, help="Engine.load's geometry (defaul
 ap.add_argument("--trace-batch", action="store_true",
                 help="lpb: the traced run with Engine.set_trace_batch on (tw_lp_batch<true> records the due runs)")
 ap.add_argument("--quantiles", action="store_true", help="also Engine.measure_quantiles: p50 / p99 / p99.9")
+ap.add_argument("--series", action="store_true",
+                help="also Engine.measure_series: the Pong curve, first Pongs and the round trip by send time")
+ap.add_argument("--config", default="hotspot", choices=("hotspot", "gossip"),
+                help="gossip: the propagation curve of a traced node-partitioned run, device series against lp_trace()")
+ap.add_argument("--nodes", type=int, default=1 << 20, help="--config gossip: nodes")
+ap.add_argument("--shards", type=int, default=1, help="--config gossip: shards of GPU 0 the nodes are split over")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "measure", "probe.log"))
 a = ap.parse_args()
 if a.trace_batch and a.geometry != "lpb":
@@ -80,6 +100,59 @@ def say_phases(e):
         rate = f", reads {rd / 1e9:.2f} GB, writes {wr / 1e9:.2f} GB: {(rd + wr) / ms / 1e6:.0f} GB/s" if rd and ms else ""
         say(f"    {k:12s} {ms:9.3f} ms{rate}")
 
+
+def gossip_probe():
+    """The propagation curve of a traced node-partitioned gossip run: the device
+    series (every shard bins its own nodes' TAG_RUMOR_FIRST records) beside the
+    host path it replaces, lp_trace() -- gather, sort and k-way merge of every
+    shard's records -- plus first_receipts, on the same run."""
+    N, k = a.nodes, a.shards
+    t0 = time.perf_counter()
+    scn = scenarios.gossip(n_nodes=N, seed=0)
+    say(f"gossip {N} nodes over {k} shard(s) of one GPU; scenario built in {time.perf_counter() - t0:.1f} s")
+    curve = dict(t0_us=1_000_000, bin_us=2000, n_bins=32)
+    with LPEngine(lp_scenario(scn), 0, N, int(scn.meta["lookahead_us"]), devices=[0] * k) as e:
+        e.lp_set_trace(N + 1024)
+        e.reset()
+        e.run_lp()
+        e.reset()                 # (every timed run is a second one)
+        t0 = time.perf_counter()
+        st = e.run_lp()
+        say(f"traced run: {(time.perf_counter() - t0) * 1e3:.1f} ms wall, done {st.done}")
+        for mode in ("first", "events"):
+            for i in range(3):
+                t0 = time.perf_counter()
+                tot, count, _stat = e.lp_measure_series(TAG_RUMOR_FIRST, mode=mode, **curve)
+                wall = (time.perf_counter() - t0) * 1e3
+                ph = e.measure_series_ms()
+                say(f"tw_lp_measure_series {mode} call {i}: wall {wall:.2f} ms; device: table fill {ph['first_fill']:.3f} ms, "
+                    f"binning {ph['bin']:.3f} ms (the slowest shard's)")
+            say(f"  {mode}: {tot}")
+            say(f"  count[{curve['t0_us']} + i * {curve['bin_us']} us] {count.tolist()}")
+            if mode == "first":
+                first = (tot, count)
+        for i in range(2):
+            t0 = time.perf_counter()
+            recs, emitted = e.lp_trace(cap=N + 1024)
+            t1 = time.perf_counter()
+            times, hist = first_receipts(recs, TAG_RUMOR_FIRST, lo_us=curve["t0_us"], bin_us=curve["bin_us"],
+                                         n_bins=curve["n_bins"])
+            t2 = time.perf_counter()
+            say(f"host path call {i}: lp_trace {(t1 - t0) * 1e3:.1f} ms ({emitted} records, {len(recs) * 24 / 2**20:.1f} MiB "
+                f"handed out) + first_receipts {(t2 - t1) * 1e3:.1f} ms = {(t2 - t0) * 1e3:.1f} ms")
+        tot, count = first
+        assert np.array_equal(hist, count) and tot["counted"] == len(times) and tot["truncated"] == 0
+        assert (tot["t_min"], tot["t_max"]) == (int(times[0]), int(times[-1]))
+        say(f"the device curve equals first_receipts over lp_trace(): {tot['counted']} nodes reached, "
+            f"{tot['t_min']} .. {tot['t_max']} us")
+
+
+if a.config == "gossip":
+    gossip_probe()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    sys.exit(0)
 
 scn = scenarios.hotspot(n_senders=S, n_replicas=R, msg_num=M, drawer=draw_link_table)
 with Engine(0) as e:
@@ -146,6 +219,36 @@ with Engine(0) as e:
             b = (int(v["lo_us"]) - spec["lo_us"]) // spec["bin_us"]
             if total["underflow"] == 0 and 0 <= b < spec["n_bins"]:
                 assert edges[b] <= q * (qpairs - 1) // 1000000 < edges[b + 1], (q, b)
+    if a.series:
+        # 16 bins over the run: the sends are 1 ms apart from 1 ms on, the Pongs follow 4 .. 9 ms behind
+        width = max((M + 12) * 1000 // 16, 1)
+        series = {"pong curve": dict(tag=TAG_PONG, mode="events", t0_us=0, bin_us=width, n_bins=16),
+                  "first pongs": dict(tag=TAG_PONG, mode="first", t0_us=0, bin_us=width, n_bins=16),
+                  "round trip by send time": dict(tag=TAG_PING_SENT, tag_to=TAG_PONG, mode="latency", t0_us=0,
+                                                  bin_us=width, n_bins=16)}
+        series_got = {}
+        for what, sp in series.items():
+            kw = dict(t0_us=sp["t0_us"], bin_us=sp["bin_us"], n_bins=sp["n_bins"], mode=sp["mode"], tag_to=sp.get("tag_to", 0))
+            for per_replica in (True, True, True, False):
+                t0 = time.perf_counter()
+                got = e.measure_series(sp["tag"], per_replica=per_replica, **kw)
+                wall = (time.perf_counter() - t0) * 1e3
+                ph = e.measure_series_ms()
+                say(f"tw_measure_series {what}{'' if per_replica else ' without per_replica'}: wall {wall:.2f} ms, device "
+                    f"{sum(ph.values()):.3f} ms = join with emit {ph['join_emit']:.3f} + table fill {ph['first_fill']:.3f} + "
+                    f"binning {ph['bin']:.3f} + latency fold {ph['latency_fold']:.3f}")
+                if per_replica:
+                    series_got[what] = got
+                else:
+                    assert got[0] == series_got[what][0] and np.array_equal(got[1], series_got[what][1])
+            stot, scount, sstat = series_got[what][:3]
+            say(f"  {stot}")
+            say(f"  count[i * {width} us] {scount.tolist()}")
+            if sstat is not None:
+                mean = [int(s) // int(c) if c else None for s, c in zip(sstat["sum_us"], scount)]
+                say(f"  mean round trip by send-time bin (us) {mean}")
+                say(f"  max  round trip by send-time bin (us) {[int(x) if c else None for x, c in zip(sstat['max_us'], scount)]}")
+                assert stot["counted"] == total["pairs"]
     say(f"hist[{spec['lo_us']} + i * {spec['bin_us']} us] {hist.tolist()}")
     assert total["pairs"] == S * M * R and total["truncated"] == 0, total
 
@@ -180,6 +283,12 @@ with Engine(0) as e:
             assert qtot.tolist() == [tuple(x) for x in wtot]
         say(f"device per-replica quantiles of the {n} sampled replicas equal quantile_reference"
             + ("; so does the batch's" if n == R else ""))
+    if a.series:
+        for what, sp in series.items():
+            _t, _c, _s, wper, wrows = series_reference(recs, emitted, cap, sp)
+            _tot, _count, _stat, sper, srows = series_got[what]
+            assert sper[sample].tobytes() == wper.tobytes() and np.array_equal(srows[sample], wrows), what
+        say(f"device per-replica series of the {n} sampled replicas equal series_reference")
 
 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
 with open(a.out, "w") as f:
