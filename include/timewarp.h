@@ -757,6 +757,35 @@ int tw_prefix_stats(tw_ctx* ctx, int64_t* t0_us, uint64_t* events_per_replica, u
  * pointer may be NULL. */
 int tw_prefix_clean_stats(tw_ctx* ctx, uint32_t* claimed_slots, uint64_t* rows_skipped,
                           uint64_t* bytes_stored_per_replica, uint32_t* verified, uint64_t* audit_mismatches);
+/* Further rows an apply leaves unstored, by class.  HDR: the header quad of a
+ * claimed slot, when the verifying sweep ended every replica it carried out
+ * (it then stored no thread header).  RUN: the run entry of a kill wake the
+ * sweep compared with the snapshot's.  RESET: a row of the node variables,
+ * hashes, listener bindings or timeout marks whose snapshot value is the one
+ * tw_reset has just left there; a cached apply is the first device work behind
+ * a tw_reset, so these are skipped whether or not the last run verified.  The
+ * pilot's apply skips nothing.  tw_prefix_clean_stats keeps counting the rows
+ * of its own rule alone; bytes_stored here is what the last apply really
+ * stored per replica.  class_rows / class_bytes: the cached snapshot's rows by
+ * class (0: none of these, 1: tw_prefix_clean_stats' rows, 2: HDR, 3: RUN, 4:
+ * RESET), from the host's classification.  The audit hook covers every class.
+ * TW_TEST_PREFIX_ROWS=0 in the environment when the context is made turns
+ * classes 2 - 4 off.  Of the context's first device. */
+typedef struct tw_prefix_rows {
+    uint64_t rows_hdr, rows_run, rows_reset;    /* rows the last tw_run's apply skipped    */
+    uint64_t bytes_hdr, bytes_run, bytes_reset; /* ... their bytes per replica             */
+    uint64_t bytes_stored;                      /* bytes that apply stored per replica     */
+    uint64_t class_rows[5], class_bytes[5];
+    /* How that apply ran: 0 no apply, 1 one workgroup per row and span (the
+     * pilot's; TW_TEST_PREFIX_LIST=0), 2 over the list of the (row, span) pairs
+     * it stores.  Form 2: the workgroups the host launched, from its copy of
+     * the sweep's flags, and the pairs the device listed from its own.  With
+     * TW_TEST_PREFIX_AUDIT=1: the rows the device's flags let the apply skip,
+     * by class (index as class_rows; 1 is tw_prefix_clean_stats' rows_skipped). */
+    uint64_t apply_form, host_pairs, list_pairs;
+    uint64_t audit_rows[5];
+} tw_prefix_rows;
+int tw_prefix_rows_stats(tw_ctx* ctx, tw_prefix_rows* out);
 
 /* Testing hook: from the next tw_reset on, start every replica's insertion
  * counter at seq0 and its thread counter at tid0 (>= 1; main is tid 0), so the

@@ -961,6 +961,11 @@ int tw_prefix_clean_stats(tw_ctx* c, uint32_t* claimed_slots, uint64_t* rows_ski
                                  audit_mismatches);
 }
 
+int tw_prefix_rows_stats(tw_ctx* c, tw_prefix_rows* out) {
+    if (!c || c->sh.empty()) return TW_ERR_INVALID;
+    return sh_prefix_rows_stats(c->sh[0], out);
+}
+
 int tw_sweep_stats(tw_ctx* c, uint64_t* killers, uint64_t* victims, uint64_t* refused_replicas) {
     if (!c) return TW_ERR_INVALID;
     uint64_t k = 0, v = 0, f = 0;

@@ -270,6 +270,12 @@ int sh_create(int device, tw_shard** out) {
     // testing hook: TW_TEST_PREFIX_AUDIT=1 follows every apply that may skip
     // rows with a read-only kernel over the skipped rows (tw_prefix_clean_stats)
     if (const char* a = getenv("TW_TEST_PREFIX_AUDIT")) c->px.audit = atoi(a) != 0;
+    // ... and TW_TEST_PREFIX_ROWS=0 leaves the apply the rows of §3o alone to
+    // skip (no header, run-entry or reset-valued rows: the A/B arm of §3v)
+    if (const char* a = getenv("TW_TEST_PREFIX_ROWS")) c->px.rows_on = atoi(a) != 0;
+    // ... and TW_TEST_PREFIX_LIST=0 keeps a cached apply on the early-exit grid
+    // (one workgroup per row and span, those of a skipped row return)
+    if (const char* a = getenv("TW_TEST_PREFIX_LIST")) c->px.list_on = atoi(a) != 0;
     // testing hook: TW_TEST_SWEEP_SLOW=1 keeps every replica on tw_sweep_apply's
     // general path (no clean bits, no terminal path: the A/B arm of §3t)
     if (const char* a = getenv("TW_TEST_SWEEP_SLOW")) c->sw.slow = atoi(a) != 0;
@@ -811,28 +817,79 @@ static int run_round(tw_shard* c, int n, int64_t t_end, uint64_t limit, uint32_t
 // claimed slots' row tags, cleared dirty bytes and flag words, in one device
 // block.  Optional: without a sweep time behind the prefix, a claimable
 // position or the memory, every apply stores every row, as before.
+//
+// And every row's class (§3v): with the table, the claimed slots' header rows
+// and the claimable positions' run entries; with or without it, the rows that
+// hold what tw_reset leaves (the reset values read back from the load's own
+// device copies).  The classes and the audit's count are a block of their own.
 static int build_clean(tw_shard* c, const std::vector<tw::PrefixRow>& rows, const uint64_t* sc) {
     const Dev& d = c->d;
     hipStream_t st = c->stream;
     Prefix::Snap& sn = c->px.snap;
-    if (!c->sw.tab.stub || c->sw.times.empty() || c->sw.stub_h.size() != (size_t)d.n_insns + 1) return TW_OK;
-    const uint32_t stop = (uint32_t)c->sw.times.size() - 1u;
-    const int64_t T = c->sw.times[stop];
-    if (T <= c->px.t0 - 1) return TW_OK;
+    const bool table = c->sw.tab.stub && !c->sw.times.empty() && c->sw.stub_h.size() == (size_t)d.n_insns + 1 &&
+                       c->sw.times.back() > c->px.t0 - 1;
+    const uint32_t stop = table ? (uint32_t)c->sw.times.size() - 1u : 0u;
+    const int64_t T = table ? c->sw.times[stop] : 0;
     std::vector<uint8_t> snap(sn.bytes);
+    std::vector<int64_t> nvi(c->nv_init ? 4ull * d.N : 0);
+    std::vector<uint32_t> lsi(c->listen_init ? d.N : 0);
     HIPCHK(hipMemcpyAsync(snap.data(), sn.tab.snap, sn.bytes, hipMemcpyDeviceToHost, st));
+    if (!nvi.empty()) HIPCHK(hipMemcpyAsync(nvi.data(), c->nv_init, 8 * nvi.size(), hipMemcpyDeviceToHost, st));
+    if (!lsi.empty()) HIPCHK(hipMemcpyAsync(lsi.data(), c->listen_init, 4 * lsi.size(), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     const tw::CleanLayout L = tw::clean_layout(d);
-    const tw::CleanPlan plan = tw::clean_build(L, rows.data(), rows.size(), snap.data(), snap.size(), sc + SC_RH0,
-                                               sc + SC_RC0, c->sw.stub_h.data(), T);
+    tw::CleanPlan plan;
+    if (table)
+        plan = tw::clean_build(L, rows.data(), rows.size(), snap.data(), snap.size(), sc + SC_RH0, sc + SC_RC0,
+                               c->sw.stub_h.data(), T);
+    // what sh_reset's memsets and tw_init_kernel leave in a replica context
+    const tw::ResetLayout rs{(uint64_t)(uintptr_t)d.nvars, (uint64_t)(uintptr_t)d.hash, (uint64_t)(uintptr_t)d.bind,
+                             (uint64_t)(uintptr_t)d.bind_own, (uint64_t)(uintptr_t)d.bind_rel,
+                             (uint64_t)(uintptr_t)d.tmo_done, d.N, d.T, nvi.empty() ? nullptr : nvi.data(),
+                             lsi.empty() ? nullptr : lsi.data(), 0xFFFFFFFFu, 0xFFFFFFFEu};
+    tw::RowClasses rc = tw::clean_classes(L, rows.data(), rows.size(), snap.data(), snap.size(), plan, &rs);
+    if (!c->px.rows_on)  // (TW_TEST_PREFIX_ROWS=0: the rows of §3o alone)
+        for (size_t i = 0; i < rc.cls.size(); ++i)
+            if (rc.cls[i] > tw::RC_BODY) {
+                --rc.n[rc.cls[i]]; ++rc.n[tw::RC_NONE];
+                rc.bytes[rc.cls[i]] -= rows[i].es; rc.bytes[tw::RC_NONE] += rows[i].es;
+                rc.cls[i] = tw::RC_NONE;
+                rc.tag[i] = tw::PCL_NO_SLOT;
+            }
+    {   // the audit's counts, the list's count, the list (a pair per row and span), the classes
+        uint64_t pairs[tw::RC_COUNT] = {0, 0, 0, 0, 0}, all = 0;
+        for (size_t i = 0; i < rows.size(); ++i) pairs[rc.cls[i]] += tw::prefix_row_spans(rows[i].dst, rows[i].es, d.R);
+        for (uint64_t p : pairs) all += p;
+        const bool list = c->px.list_on && c->px.rows_on && all <= 0x7FFFFFFFull;  // (TW_TEST_PREFIX_ROWS=0: as §3o had it)
+        const size_t o_cls = 64 + (list ? 8 * (size_t)all : 0);  // (the counts: RC_COUNT words, then the list's)
+        void* blk = nullptr;
+        if (hipMalloc(&blk, o_cls + rc.cls.size()) != hipSuccess) {
+            (void)hipGetLastError();  // (no memory: no skipping, not an error of the run)
+            return TW_OK;
+        }
+        HIPCHK(hipMemset(blk, 0, 64));
+        HIPCHK(hipMemcpy((uint8_t*)blk + o_cls, rc.cls.data(), rc.cls.size(), hipMemcpyHostToDevice));
+        sn.audit = (unsigned long long*)blk;
+        sn.cls = (const uint8_t*)blk + o_cls;
+        if (list) {
+            sn.tab.list_n = (uint32_t*)((uint8_t*)blk + 48);
+            sn.tab.list = (uint2*)((uint8_t*)blk + 64);
+            sn.tab.list_cap = (uint32_t)all;
+        }
+        for (int k = 0; k < tw::RC_COUNT; ++k) {
+            sn.class_rows[k] = rc.n[k]; sn.class_bytes[k] = rc.bytes[k]; sn.class_pairs[k] = pairs[k];
+        }
+        sn.pairs16 = tw::prefix_row_spans(0, 16, d.R);
+    }
     if (plan.slots.empty()) return TW_OK;
-    const std::vector<uint32_t> tag = tw::clean_tags(L, rows.data(), rows.size(), plan.slots);
+    const std::vector<uint32_t>& tag = rc.tag;
     const tw::CleanEffects fx = tw::clean_effects(L, rows.data(), rows.size(), snap.data(), snap.size(),
                                                   c->sw.stub_h.data(), plan);
     const size_t S4 = ((size_t)d.S + 3u) & ~(size_t)3u;
     const size_t o_win = sizeof(tw::KillEnt) * plan.ents.size(), o_tag = o_win + sizeof(tw::KillWin) * TW_RUNS,
-                 o_dirty = o_tag + 4 * tag.size(), o_audit = (o_dirty + S4 + 4 * CF_COUNT + 7u) & ~(size_t)7u,
-                 o_eff = (o_audit + 8 + 15u) & ~(size_t)15u, total = o_eff + sizeof(tw::EffEnt) * fx.eff.size();
+                 o_dirty = o_tag + 4 * tag.size(),
+                 o_eff = (o_dirty + S4 + 4 * CF_COUNT + 15u) & ~(size_t)15u,
+                 total = o_eff + sizeof(tw::EffEnt) * fx.eff.size();
     Prefix::Snap::Clean& cl = sn.clean;
     if (hipMalloc(&cl.dev, total) != hipSuccess || hipHostMalloc((void**)&cl.h, S4 + 4 * CF_COUNT) != hipSuccess) {
         (void)hipGetLastError();  // (no memory: no skipping, not an error of the run)
@@ -856,7 +913,10 @@ static int build_clean(tw_shard* c, const std::vector<tw::PrefixRow>& rows, cons
     cl.tag = (const uint32_t*)(b + o_tag);
     cl.dirty = b + o_dirty;
     cl.cflags = (uint32_t*)(b + o_dirty + S4);
-    cl.audit = (unsigned long long*)(b + o_audit);
+    for (size_t i = 0; i < rc.cls.size(); ++i) {  // (for the host's count of what an apply skips)
+        if (rc.cls[i] == tw::RC_HDR) cl.hdr_tags.push_back(rc.tag[i]);
+        if (rc.cls[i] == tw::RC_RUN) cl.run_tags.push_back(rc.tag[i]);
+    }
     // the effects rows, and a clean bit per table position and replica: without
     // the memory the sweep applies every entry the general way
     HIPCHK(hipMemcpy(b + o_eff, fx.eff.data(), sizeof(tw::EffEnt) * fx.eff.size(), hipMemcpyHostToDevice));
@@ -945,21 +1005,45 @@ static int run_prefix(tw_shard* c, uint64_t limit, uint32_t budget, bool verifie
     // `skip` is the host's side of the validity rule, CF_VALID the device's.
     // The flags are consumed: cleared behind the apply, inside its timed pair.
     const Prefix::Snap::Clean& cl = px.snap.clean;
-    const bool skip = hit && cl.dev && verified;
+    // §3v: a cached apply is the first device work behind tw_reset (run_prefix
+    // is a fresh tw_run's, and no call between the two writes the arrays
+    // tw_reset fills), so the rows that hold tw_reset's values stay as they
+    // are, verified or not; the pilot's apply stores everything.
+    const bool skip = hit && cl.dev && px.snap.cls && verified;
+    const bool rst = hit && px.snap.cls && px.snap.class_rows[tw::RC_RESET] != 0;
     tw::PrefixTab tab = px.snap.tab;
     px.rows_skipped = 0;
+    px.rows = Prefix::Rows{};
+    if (skip || rst) tab.cls = px.snap.cls;
+    tab.reset = rst ? 1u : 0u;
     if (skip) {
         tab.tag = cl.tag; tab.dirty = cl.dirty; tab.cflags = cl.cflags;
         const uint32_t* hf = (const uint32_t*)(cl.h + cl.S);
-        if (hf[CF_VALID])
+        if (hf[CF_VALID] == 1u) {
             for (uint32_t s : cl.slots) px.rows_skipped += cl.h[s] ? 0u : 3u;
+            for (uint32_t s : cl.run_tags) px.rows.n[1] += cl.h[s] ? 0u : 1u;
+            if (hf[CF_HDR_OK] == 1u)
+                for (uint32_t s : cl.hdr_tags) px.rows.n[0] += cl.h[s] ? 0u : 1u;
+        }
     }
+    if (rst) px.rows.n[2] = px.snap.class_rows[tw::RC_RESET];
+    px.rows.bytes[0] = 16u * px.rows.n[0];
+    px.rows.bytes[1] = 16u * px.rows.n[1];
+    px.rows.bytes[2] = rst ? px.snap.class_bytes[tw::RC_RESET] : 0u;
     px.bytes_stored = px.snap.bytes - 16u * px.rows_skipped;
+    px.rows.stored = px.bytes_stored - px.rows.bytes[0] - px.rows.bytes[1] - px.rows.bytes[2];
+    // the compact form's grid: the pairs of the rows this apply stores, as the host counts them
+    uint64_t pairs = 0;
+    for (uint64_t p : px.snap.class_pairs) pairs += p;
+    pairs -= px.snap.pairs16 * (px.rows_skipped + px.rows.n[0] + px.rows.n[1]) +
+             (rst ? px.snap.class_pairs[tw::RC_RESET] : 0u);
+    px.rows.form = (tab.list && tab.cls) ? 2u : 1u;
+    px.rows.pairs = px.rows.form == 2u ? pairs : 0u;
     int rc = c->times.timed(st, [&]() -> int {
-        HIPCHK(prefix_apply(tab, d.R, px.snap.max_es, st));
-        if (skip && px.audit) {
-            HIPCHK(hipMemsetAsync(cl.audit, 0, 8, st));
-            HIPCHK(prefix_audit(tab, d.R, px.snap.max_es, cl.audit, st));
+        HIPCHK(prefix_apply(tab, d.R, px.snap.max_es, (uint32_t)pairs, st));
+        if (tab.cls && px.audit) {
+            HIPCHK(hipMemsetAsync(px.snap.audit, 0, 8 * tw::RC_COUNT, st));
+            HIPCHK(prefix_audit(tab, d.R, px.snap.max_es, px.snap.audit, st));
             px.audited = true;
         }
         if (cl.dev) HIPCHK(hipMemsetAsync(cl.dirty, 0, cl.S + 4 * CF_COUNT, st));
@@ -1013,6 +1097,7 @@ int sh_run(tw_shard* c, int64_t t_end_us, uint64_t max_events, tw_stats* out) {
     c->px.verified = c->px.last_verified = false;
     if (was_fresh) c->px.chain = false;
     c->px.rows_skipped = c->px.bytes_stored = 0;
+    c->px.rows = Prefix::Rows{};
     c->px.audited = false;
     if (c->lpm.lpb) {
         // the batched window loop runs every replica to quiescence
@@ -1292,13 +1377,38 @@ int sh_prefix_clean_stats(tw_shard* c, uint32_t* claimed, uint64_t* rows_skipped
     if (verified) *verified = c->px.last_verified ? 1u : 0u;
     if (audit) {
         unsigned long long n = 0;
-        if (c->px.audited && cl.audit) {
+        if (c->px.audited && c->px.snap.audit) {
             HIPCHK(hipSetDevice(c->device));
-            HIPCHK(hipMemcpyAsync(&n, cl.audit, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(&n, c->px.snap.audit, 8, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
         }
         *audit = n;
     }
+    return TW_OK;
+}
+
+int sh_prefix_rows_stats(tw_shard* c, tw_prefix_rows* out) {
+    if (!c || !out) return TW_ERR_INVALID;
+    if (!c->loaded) return TW_ERR_STATE;
+    std::memset(out, 0, sizeof(*out));
+    const Prefix& px = c->px;
+    out->rows_hdr = px.rows.n[0]; out->rows_run = px.rows.n[1]; out->rows_reset = px.rows.n[2];
+    out->bytes_hdr = px.rows.bytes[0]; out->bytes_run = px.rows.bytes[1]; out->bytes_reset = px.rows.bytes[2];
+    out->bytes_stored = px.rows.stored;
+    out->apply_form = px.rows.form;
+    out->host_pairs = px.rows.pairs;
+    // the device's own counts: the list it wrote, and (hook on) the rows it skipped by class
+    if (px.snap.ok && px.snap.audit && px.rows.form) {
+        unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipMemcpyAsync(h, px.snap.audit, 64, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (px.rows.form == 2u) out->list_pairs = (uint32_t)h[6];
+        if (px.audited)
+            for (int k = 1; k < 5; ++k) out->audit_rows[k] = h[k];
+    }
+    if (px.snap.ok && px.snap.cls)
+        for (int k = 0; k < 5; ++k) { out->class_rows[k] = px.snap.class_rows[k]; out->class_bytes[k] = px.snap.class_bytes[k]; }
     return TW_OK;
 }
 

@@ -13,8 +13,15 @@
 //   apply   one workgroup per (row, span of the row): the row's value to the
 //           span's replicas; store-only, 16 B per lane where the row allows.
 //           A row the last sweep proved unwritten in every replica since the
-//           apply before is left as it is: its workgroups return
-//   audit   the testing hook's check of those rows (read-only)
+//           apply before, or that holds what tw_reset has
+//           just left there, is left as it is: its workgroups return.  The
+//           pilot's apply, and a cached one's early-exit form
+//   list, apply_list
+//           a cached apply's compact form (§3v): one thread per row writes the
+//           (row, span) pairs of the rows that are stored, then one workgroup
+//           per listed pair stores it: no workgroup for a row left as it is
+//   audit   the testing hook's check of those rows (read-only), and its count
+//           of them by class
 //
 // Every per-replica array is replica-minor, so a row is R contiguous elements.
 // Plain C++ and vector stores only.
@@ -51,30 +58,34 @@ __device__ __forceinline__ uint32_t word_of(uint4 v, uint32_t i) {
     return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w;
 }
 
-// Row blockIdx.x, bytes [blockIdx.y * SPAN, + SPAN) of its 16-byte-aligned
-// body.  A row of 4-byte (1-byte) elements starts on any dword (byte) when R
-// is no multiple of 4 (16): the bytes in front of the first 16-byte boundary
-// and behind the last go out as dwords (bytes) from the row's first workgroup.
-// The value is read once per wave, through the scalar cache (the row is
-// uniform over the workgroup); only rows wider than 16 B (the handler-stack
-// overflow, FXQ > 1) load their quad per lane.
-// quad 1 - 3 of a claimed slot that no replica wrote since the last apply (§3o)
-__device__ __forceinline__ bool row_clean(const PrefixTab& t, uint32_t row) {
-    if (!t.tag) return false;
-    const uint32_t s = t.tag[row];
-    return s != PCL_NO_SLOT && t.cflags[CF_VALID] != 0u && t.dirty[s] == 0;
+// The class under which the apply leaves `row` unstored, RC_NONE: it stores it
+// (§3o, §3v; prefix_dev.hpp has the rule).  The device's own flag words and
+// dirty bytes decide for RC_BODY, RC_HDR and RC_RUN.
+__device__ __forceinline__ uint32_t row_skipped(const PrefixTab& t, uint32_t row) {
+    if (!t.cls) return RC_NONE;
+    const uint32_t k = t.cls[row];
+    if (k == RC_NONE) return RC_NONE;
+    if (k == RC_RESET) return t.reset ? k : (uint32_t)RC_NONE;
+    if (!t.dirty || t.cflags[k == RC_HDR ? CF_HDR_OK : CF_VALID] != 1u) return RC_NONE;
+    return t.dirty[t.tag[row]] == 0 ? k : (uint32_t)RC_NONE;
 }
 
-__global__ void __launch_bounds__(256) tw_prefix_apply(PrefixTab t, uint32_t R) {
-    if (row_clean(t, blockIdx.x)) return;
-    const PrefixRow e = t.rows[blockIdx.x];
+// One workgroup's share: bytes [span * SPAN, + SPAN) of the 16-byte-aligned
+// body of `row`.  A row of 4-byte (1-byte) elements starts on any dword (byte)
+// when R is no multiple of 4 (16): the bytes in front of the first 16-byte
+// boundary and behind the last go out as dwords (bytes) from the row's first
+// workgroup.  The value is read once per wave, through the scalar cache (the
+// row is uniform over the workgroup); only rows wider than 16 B (the
+// handler-stack overflow, FXQ > 1) load their quad per lane.
+__device__ __forceinline__ void store_span(const PrefixTab& t, uint32_t R, uint32_t row, uint32_t span) {
+    const PrefixRow e = t.rows[row];
     const uint32_t es = e.es;
     const uint64_t len = (uint64_t)R * es;
     const uint64_t mis = (16u - (uint32_t)(e.dst & 15u)) & 15u;
     const uint64_t head = mis < len ? mis : len;
     const uint64_t body = (len - head) & ~15ull;
-    const uint64_t b0 = (uint64_t)blockIdx.y * TW_PREFIX_SPAN;
-    if (blockIdx.y != 0 && b0 >= body) return;
+    const uint64_t b0 = (uint64_t)span * TW_PREFIX_SPAN;
+    if (span != 0 && b0 >= body) return;
     const uint8_t* src = t.snap + e.off;
     uint4 v = make_uint4(0u, 0u, 0u, 0u);
     if (es == 1) {
@@ -97,7 +108,7 @@ __global__ void __launch_bounds__(256) tw_prefix_apply(PrefixTab t, uint32_t R) 
         for (uint64_t o = b0 + (uint64_t)threadIdx.x * 16u; o < b1; o += 256u * 16u)
             *(uint4 GAS*)(dst + head + o) = *(const uint4 GAS*)(gp(t.snap) + e.off + (uint32_t)((head + o) % es));
     }
-    if (blockIdx.y != 0) return;
+    if (span != 0) return;
     const uint64_t tail0 = head + body, tail = len - tail0;  // (both edges: < 16 bytes each)
     if (es == 1) {
         if (threadIdx.x < head) dst[threadIdx.x] = (uint8_t)v.x;
@@ -112,20 +123,74 @@ __global__ void __launch_bounds__(256) tw_prefix_apply(PrefixTab t, uint32_t R) 
     }
 }
 
-// The rows tw_prefix_apply skipped (its own test, on the flags it read), all
-// R elements against the snapshot's quad.  Tagged rows are record quads:
-// 16-byte elements from a 16-byte-aligned address.
+// The early-exit form: one workgroup per (row, span of the widest row); those
+// of a skipped row, and those past a narrower row's end, return.
+__global__ void __launch_bounds__(256) tw_prefix_apply(PrefixTab t, uint32_t R) {
+    if (row_skipped(t, blockIdx.x) != RC_NONE) return;
+    store_span(t, R, blockIdx.x, blockIdx.y);
+}
+
+// The compact form (§3v): tw_prefix_list writes the (row, span) pairs of the
+// rows the apply stores, on the device's own flags; tw_prefix_apply_list is
+// launched over about that many workgroups (the host's count, from its copy of
+// the flags) and walks the list by its grid, so every pair is stored whatever
+// the grid.  A row's pairs are contiguous; rows come in any order.
+__global__ void __launch_bounds__(256) tw_prefix_list(PrefixTab t, uint32_t R) {
+    const uint32_t row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= t.n_rows || row_skipped(t, row) != RC_NONE) return;
+    const PrefixRow e = t.rows[row];
+    const uint32_t ns = prefix_row_spans(e.dst, e.es, R);
+    const uint32_t at = __hip_atomic_fetch_add(gp(t.list_n), ns, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (uint32_t s = 0; s < ns && at + s < t.list_cap; ++s) gp(t.list)[at + s] = make_uint2(row, s);
+}
+
+__global__ void __launch_bounds__(256) tw_prefix_apply_list(PrefixTab t, uint32_t R) {
+    const uint32_t n = *t.list_n < t.list_cap ? *t.list_n : t.list_cap;
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const uint2 p = t.list[i];
+        store_span(t, R, p.x, p.y);
+    }
+}
+
+// The rows tw_prefix_apply skipped (its own test, on the flags it read): every
+// element of the row against the snapshot's.  Elements of 16, 8, 4 bytes and
+// single bytes, each loaded whole from its own naturally aligned address, so a
+// row that starts off a 16-byte boundary (R no multiple of 16) needs no head
+// or tail: workgroup blockIdx.y takes elements [i0, i1) of the R.
+// count[0] += the elements that differ; count[class] += 1 per skipped row (the
+// device's own count of what its flags let the apply skip).
 __global__ void __launch_bounds__(256) tw_prefix_audit(PrefixTab t, uint32_t R, unsigned long long* count) {
-    if (!row_clean(t, blockIdx.x)) return;
+    const uint32_t k = row_skipped(t, blockIdx.x);
+    if (k == RC_NONE) return;
+    if (blockIdx.y == 0 && threadIdx.x == 0)
+        __hip_atomic_fetch_add(gp(count) + k, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const PrefixRow e = t.rows[blockIdx.x];
-    const uint4 v = *(const uint4*)(t.snap + e.off);
-    const uint4 GAS* dst = (const uint4 GAS*)(uintptr_t)e.dst;
-    const uint64_t i0 = (uint64_t)blockIdx.y * (TW_PREFIX_SPAN / 16u);
-    const uint64_t i1 = i0 + TW_PREFIX_SPAN / 16u < R ? i0 + TW_PREFIX_SPAN / 16u : R;
+    const uint32_t es = e.es;
+    if (es > 16) return;  // (no class has such a row)
+    const uint64_t per = TW_PREFIX_SPAN / es;
+    const uint64_t i0 = (uint64_t)blockIdx.y * per;
+    const uint64_t i1 = i0 + per < R ? i0 + per : R;
+    const uint8_t* src = t.snap + e.off;
+    const uint8_t GAS* dst = (const uint8_t GAS*)(uintptr_t)e.dst;
     uint32_t bad = 0;
-    for (uint64_t i = i0 + threadIdx.x; i < i1; i += 256u) {
-        const uint4 x = dst[i];
-        bad += (x.x != v.x || x.y != v.y || x.z != v.z || x.w != v.w) ? 1u : 0u;
+    if (es == 16) {
+        const uint4 v = *(const uint4*)src;
+        for (uint64_t i = i0 + threadIdx.x; i < i1; i += 256u) {
+            const uint4 x = ((const uint4 GAS*)dst)[i];
+            bad += (x.x != v.x || x.y != v.y || x.z != v.z || x.w != v.w) ? 1u : 0u;
+        }
+    } else if (es == 8) {
+        const uint2 v = *(const uint2*)src;
+        for (uint64_t i = i0 + threadIdx.x; i < i1; i += 256u) {
+            const uint2 x = ((const uint2 GAS*)dst)[i];
+            bad += (x.x != v.x || x.y != v.y) ? 1u : 0u;
+        }
+    } else if (es == 4) {
+        const uint32_t v = *(const uint32_t*)src;
+        for (uint64_t i = i0 + threadIdx.x; i < i1; i += 256u) bad += ((const uint32_t GAS*)dst)[i] != v ? 1u : 0u;
+    } else if (es == 1) {
+        const uint8_t v = *src;
+        for (uint64_t i = i0 + threadIdx.x; i < i1; i += 256u) bad += dst[i] != v ? 1u : 0u;
     }
     for (int m = 32; m >= 1; m >>= 1) bad += __shfl_xor(bad, m, 64);
     if ((threadIdx.x & 63u) == 0 && bad)
@@ -198,8 +263,16 @@ hipError_t prefix_take(const PrefixTab& t, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t prefix_apply(const PrefixTab& t, uint32_t R, uint32_t max_es, hipStream_t st) {
+hipError_t prefix_apply(const PrefixTab& t, uint32_t R, uint32_t max_es, uint32_t pairs, hipStream_t st) {
     if (t.n_rows == 0 || R == 0) return hipSuccess;
+    if (t.list && t.cls) {
+        hipError_t e = hipMemsetAsync(t.list_n, 0, 4, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(tw_prefix_list, dim3((t.n_rows + 255u) / 256u), dim3(256), 0, st, t, R);
+        const uint32_t grid = pairs < 1u ? 1u : pairs > t.list_cap ? t.list_cap : pairs;
+        hipLaunchKernelGGL(tw_prefix_apply_list, dim3(grid), dim3(256), 0, st, t, R);
+        return hipGetLastError();
+    }
     // rows x spans: the whole chip stores at once (C3: ~70k rows of 256 KB - 1 MB)
     const uint64_t spans = ((uint64_t)R * max_es + TW_PREFIX_SPAN - 1) / TW_PREFIX_SPAN;
     hipLaunchKernelGGL(tw_prefix_apply, dim3(t.n_rows, (uint32_t)(spans ? spans : 1)), dim3(256), 0, st, t, R);
@@ -207,7 +280,7 @@ hipError_t prefix_apply(const PrefixTab& t, uint32_t R, uint32_t max_es, hipStre
 }
 
 hipError_t prefix_audit(const PrefixTab& t, uint32_t R, uint32_t max_es, unsigned long long* count, hipStream_t st) {
-    if (t.n_rows == 0 || R == 0 || !t.tag) return hipSuccess;
+    if (t.n_rows == 0 || R == 0 || !t.cls) return hipSuccess;
     const uint64_t spans = ((uint64_t)R * max_es + TW_PREFIX_SPAN - 1) / TW_PREFIX_SPAN;
     hipLaunchKernelGGL(tw_prefix_audit, dim3(t.n_rows, (uint32_t)(spans ? spans : 1)), dim3(256), 0, st, t, R, count);
     return hipGetLastError();

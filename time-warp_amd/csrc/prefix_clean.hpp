@@ -46,7 +46,11 @@ constexpr uint32_t PCL_NO_SLOT = 0xFFFFFFFFu;  // a row's tag: not a claimed slo
 // not checked against the whole table (not attempted, refused, a window the
 // table's does not fit).  CF_VALID: published by the sweep's last kernel --
 // every replica checked, none with work left; consumed by the next apply.
-enum { CF_ALL_DIRTY, CF_VALID, CF_COUNT };
+// CF_HDR_OK (§3v): published with it -- CF_VALID, and every replica the sweep
+// carried out was terminal, so that no sweep kernel stored a thread header
+// (until then the word is finalize's: CFH_GENERAL where one took the general path).
+enum { CF_ALL_DIRTY, CF_VALID, CF_HDR_OK, CF_COUNT };
+constexpr uint32_t CFH_GENERAL = 2u;
 
 // One run position of the table: four quads, read by the sweep as such.
 struct KillEnt {
@@ -324,6 +328,108 @@ inline std::vector<uint32_t> clean_tags(const CleanLayout& L, const PrefixRow* r
         if (s < L.S && claimed[s]) tag[i] = (uint32_t)s;
     }
     return tag;
+}
+
+// The CLASS of every directory row: what lets an apply leave it
+// unstored.  RC_BODY rows are clean_tags' (same tags); the others widen it.
+//   RC_HDR    quad 0 of a claimed slot (tag: the slot): with CF_HDR_OK -- no
+//             replica's sweep took the general path, which stores dead headers
+//   RC_RUN    the run entry at a claimable table position (tag: the position's
+//             killer slot, which no other position shares; validate compares
+//             the entry and marks all of a position's slots together)
+//   RC_RESET  a row of nvars, hash, bind, bind_own, bind_rel or tmo_done whose
+//             snapshot bytes are what tw_reset has just left in that element
+//             (tag: PCL_NO_SLOT; no sweep is involved)
+enum : uint8_t { RC_NONE, RC_BODY, RC_HDR, RC_RUN, RC_RESET, RC_COUNT };
+
+// What tw_reset leaves, replica-uniform: the arrays' device addresses (replica
+// 0's first element; 0: no such array), their rows, and each element's value.
+// nvars: nv_init[i] (null: 0); hash: 0; bind: listen_init[n] (null: 0);
+// bind_own, bind_rel: the two constants; tmo_done: 0.
+struct ResetLayout {
+    uint64_t nvars, hash, bind, bind_own, bind_rel, tmo_done;
+    uint32_t N, T;                // nodes (nvars: 4 rows each); timeouts
+    const int64_t* nv_init;       // [4 * N] or null
+    const uint32_t* listen_init;  // [N] or null
+    uint32_t own0, rel0;
+};
+
+struct RowClasses {
+    std::vector<uint8_t> cls;   // [n_rows] RC_*
+    std::vector<uint32_t> tag;  // [n_rows] the slot whose dirty byte decides (RC_BODY, RC_HDR, RC_RUN), else PCL_NO_SLOT
+    uint32_t n[RC_COUNT] = {0, 0, 0, 0, 0};      // rows per class
+    uint64_t bytes[RC_COUNT] = {0, 0, 0, 0, 0};  // ... and their bytes per replica
+};
+
+// rs null: no RC_RESET rows.  A plan without claimed slots gives RC_RESET rows only.
+inline RowClasses clean_classes(const CleanLayout& L, const PrefixRow* rows, size_t n_rows, const uint8_t* snap,
+                                size_t snap_bytes, const CleanPlan& p, const ResetLayout* rs) {
+    RowClasses out;
+    out.cls.assign(n_rows, RC_NONE);
+    out.tag.assign(n_rows, PCL_NO_SLOT);
+    if (!rows || L.R == 0) { out.n[RC_NONE] = (uint32_t)n_rows; return out; }
+    std::vector<uint8_t> claimed(L.S, 0);
+    for (uint32_t s : p.slots)
+        if (s < L.S) claimed[s] = 1;
+    // claimable positions by their run entry's address
+    std::unordered_map<uint64_t, uint32_t> killer;
+    for (uint32_t j = 0; j < L.n_runs && j < p.win.size() && L.Cr; ++j) {
+        const KillWin& w = p.win[j];
+        for (uint32_t k = 0; k < w.n; ++k) {
+            if ((size_t)w.base + k >= p.ents.size()) break;
+            const KillEnt& e = p.ents[w.base + k];
+            if (e.nref == 0 || e.e[2] >= L.S || !claimed[e.e[2]]) continue;
+            const uint32_t pos = (w.pos0 + k) % L.Cr;
+            killer.emplace(L.runs + (((uint64_t)j * L.Cr + pos) * L.R) * 16u, e.e[2]);
+        }
+    }
+    const uint64_t span = L.RQ * 16u;  // bytes between a record's quads
+    // whether row r lies in a reset array of `n` rows of `es` bytes from `base`; its row index
+    auto in = [&](const PrefixRow& r, uint64_t base, uint64_t n, uint32_t es, uint64_t& ix) {
+        if (!base || r.es != es || r.dst < base) return false;
+        const uint64_t b = r.dst - base, step = L.R * es;
+        ix = b / step;
+        return b % step == 0 && ix < n;
+    };
+    for (size_t i = 0; i < n_rows; ++i) {
+        const PrefixRow& r = rows[i];
+        uint8_t c = RC_NONE;
+        if (r.es == 16) {
+            auto it = killer.find(r.dst);
+            if (it != killer.end()) {
+                c = RC_RUN;
+                out.tag[i] = it->second;
+            } else if (span && r.dst >= L.slots) {
+                const uint64_t b = r.dst - L.slots, q = b / span, off = b % span;
+                const uint64_t s = off / (L.R * 16u);
+                if (q <= 3 && off % (L.R * 16u) == 0 && s < L.S && claimed[s]) {
+                    c = q == 0 ? RC_HDR : RC_BODY;
+                    out.tag[i] = (uint32_t)s;
+                }
+            }
+        } else if (rs && snap && (uint64_t)r.off + r.es <= snap_bytes) {
+            uint64_t ix = 0;
+            const uint8_t* v = snap + r.off;
+            uint64_t want = 0;
+            bool hit = true;
+            if (in(r, rs->nvars, 4ull * rs->N, 8, ix)) want = rs->nv_init ? (uint64_t)rs->nv_init[ix] : 0ull;
+            else if (in(r, rs->hash, rs->N, 8, ix)) want = 0;
+            else if (in(r, rs->bind, rs->N, 4, ix)) want = rs->listen_init ? rs->listen_init[ix] : 0u;
+            else if (in(r, rs->bind_own, rs->N, 4, ix)) want = rs->own0;
+            else if (in(r, rs->bind_rel, rs->N, 4, ix)) want = rs->rel0;
+            else if (in(r, rs->tmo_done, rs->T, 1, ix)) want = 0;
+            else hit = false;
+            uint64_t have = 0;
+            std::memcpy(&have, v, r.es);  // (es is 1, 4 or 8; little-endian words)
+            if (hit && have == want) c = RC_RESET;
+        }
+        out.cls[i] = c;
+    }
+    for (size_t i = 0; i < n_rows; ++i) {
+        ++out.n[out.cls[i]];
+        out.bytes[out.cls[i]] += rows[i].es;
+    }
+    return out;
 }
 
 }  // namespace tw

@@ -120,11 +120,20 @@ struct Prefix {
         uint32_t max_es = 0;
         uint64_t events = 0;            // events of a replica at the snapshot
         size_t bytes = 0;               // the snapshot's bytes per replica
+        // Every row's class (prefix_clean.hpp RC_*) behind the
+        // audit's count and the compact form's list (tab.list*), one device
+        // block (audit null: none, every apply stores every row); the rows,
+        // bytes per replica and (row, span) pairs of each class, and the
+        // pairs of one 16-byte row
+        unsigned long long* audit = nullptr;
+        const uint8_t* cls = nullptr;
+        uint64_t class_rows[tw::RC_COUNT] = {0, 0, 0, 0, 0}, class_bytes[tw::RC_COUNT] = {0, 0, 0, 0, 0};
+        uint64_t class_pairs[tw::RC_COUNT] = {0, 0, 0, 0, 0}, pairs16 = 0;
         // Rows the apply may leave unstored (prefix_clean.hpp): the
         // kill table of sweep time T = Sweep::times[stop], built from this
         // snapshot; `dev` null: none.  One device block (table, windows, row
-        // tags, dirty bytes, flag words, the audit's count) and the pinned
-        // copy of the dirty bytes and flag words a verifying run leaves.
+        // tags, dirty bytes, flag words) and the pinned copy of the dirty
+        // bytes and flag words a verifying run leaves.
         struct Clean {
             void* dev = nullptr;
             const tw::KillEnt* kill = nullptr;
@@ -132,8 +141,8 @@ struct Prefix {
             const uint32_t* tag = nullptr;
             uint8_t* dirty = nullptr;           // [S], then the CF_COUNT flag words
             uint32_t* cflags = nullptr;
-            unsigned long long* audit = nullptr;
             uint8_t* h = nullptr;               // pinned: [S] dirty bytes + flag words
+            std::vector<uint32_t> hdr_tags, run_tags;  // the tag of every RC_HDR / RC_RUN row
             // the sweep's terminal path (§3t): the effects rows (in `dev`) and the
             // clean bits, a block of their own; bits null: no memory, no such path
             const tw::EffEnt* eff = nullptr;
@@ -154,8 +163,14 @@ struct Prefix {
     bool audit = false;                 // the testing hook TW_TEST_PREFIX_AUDIT (read when the context is made)
     // of the last apply: rows left unstored, bytes stored per replica; whether the last tw_run verified
     uint64_t rows_skipped = 0, bytes_stored = 0;
+    // ... and of §3v's classes (header, run-entry and reset-valued rows, in
+    // this order): rows and bytes per replica left unstored, bytes stored
+    // form: 1 the grid over every row and span, 2 the compact list, over `pairs` workgroups
+    struct Rows { uint64_t n[3] = {0, 0, 0}, bytes[3] = {0, 0, 0}, stored = 0, pairs = 0; uint32_t form = 0; } rows;
+    bool rows_on = true;                // the testing hook TW_TEST_PREFIX_ROWS (read when the context is made)
+    bool list_on = true;                // ... and TW_TEST_PREFIX_LIST: the apply's compact form
     bool last_verified = false;
-    bool audited = false;               // the last apply ran the hook's audit (its count: Clean::audit)
+    bool audited = false;               // the last apply ran the hook's audit (its counts: Snap::audit)
 
     // anything but tw_reset, tw_run and a read-only call: the flags no longer
     // describe the replicas
@@ -164,6 +179,7 @@ struct Prefix {
     void drop() {
         if (snap.tab.rows) (void)hipFree((void*)snap.tab.rows);
         if (snap.tab.snap) (void)hipFree(snap.tab.snap);
+        if (snap.audit) (void)hipFree(snap.audit);
         if (snap.clean.dev) (void)hipFree(snap.clean.dev);
         if (snap.clean.bits) (void)hipFree(snap.clean.bits);
         if (snap.clean.h) (void)hipHostFree(snap.clean.h);
@@ -173,7 +189,7 @@ struct Prefix {
     void unload() {
         drop();
         Prefix z;
-        z.last = last; z.ms = ms; z.audit = audit;
+        z.last = last; z.ms = ms; z.audit = audit; z.rows_on = rows_on; z.list_on = list_on;
         *this = z;
     }
 };

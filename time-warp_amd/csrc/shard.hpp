@@ -47,6 +47,8 @@ TW_HIDDEN int sh_prefix_stats(tw_shard* c, int64_t* t0, uint64_t* events, uint64
 // whether that run verified, the testing hook's mismatch count
 TW_HIDDEN int sh_prefix_clean_stats(tw_shard* c, uint32_t* claimed, uint64_t* rows_skipped, uint64_t* bytes_stored,
                                     uint32_t* verified, uint64_t* audit);
+// ... and per row class of §3v: the last apply's skipped rows and bytes, the snapshot's classification
+TW_HIDDEN int sh_prefix_rows_stats(tw_shard* c, tw_prefix_rows* out);
 // live delays (tw_set_live_delays): desc = live_plan.hpp's descriptors of the
 // loaded links (null: off), seed0 = the seed of the shard's first replica;
 // TW_ERR_INVALID for a node-partitioned or batched LP shard.  sh_live_stats:

@@ -495,6 +495,8 @@ __global__ void __launch_bounds__(256) tw_sweep_finalize(Dev c, SweepTab t, int6
         int64_t next = (int64_t)(((uint64_t)*acc_at(t, c, SW_XHI, r) << 32) | *acc_at(t, c, SW_XLO, r));
         if (sweep_go(c, t, r, max_events)) {
             term = sweep_term(c, t, r) ? 1ull : 0ull;  // (as both applies saw it: live is still the event kernel's)
+            // (§3v) tw_sweep_apply stored this replica's dead headers: the next apply stores the header rows
+            if (t.kill && !term) gp(t.cflags)[CF_HDR_OK] = CFH_GENERAL;
             fast = *acc_at(t, c, SW_FAST, r);
             k = *acc_at(t, c, SW_K, r);
             v = *acc_at(t, c, SW_V, r);
@@ -555,10 +557,15 @@ __global__ void __launch_bounds__(256) tw_sweep_finalize(Dev c, SweepTab t, int6
 
 // the stop is done (a kernel of its own: every block of finalize reads the gate)
 // ... and, with a kill table: every replica was checked against all of it and
-// none has work left that could write a record after the check (§3o)
+// none has work left that could write a record after the check (§3o); and
+// whether all of them were terminal, so that no header was stored either (§3v)
 __global__ void tw_sweep_mark(Dev c, SweepTab t, uint32_t expect) {
     if (!sweep_gate(c, t, expect)) return;
-    if (t.kill) gp(t.cflags)[CF_VALID] = (gp(t.cflags)[CF_ALL_DIRTY] == 0u && gp(t.stats)[SWS_LEFT] == 0ull) ? 1u : 0u;
+    if (t.kill) {
+        const bool valid = gp(t.cflags)[CF_ALL_DIRTY] == 0u && gp(t.stats)[SWS_LEFT] == 0ull;
+        gp(t.cflags)[CF_VALID] = valid ? 1u : 0u;
+        gp(t.cflags)[CF_HDR_OK] = (valid && gp(t.cflags)[CF_HDR_OK] == 0u) ? 1u : 0u;
+    }
     gp(t.stats)[SWS_FIRED] = (unsigned long long)expect + 1ull;
 }
 

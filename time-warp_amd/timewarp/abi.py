@@ -108,6 +108,25 @@ class TwLiveDelays(C.Structure):
     ]
 
 
+class TwPrefixRows(C.Structure):
+    """tw_prefix_rows: the rows an apply leaves unstored, by class."""
+    _fields_ = [
+        ("rows_hdr", C.c_uint64),
+        ("rows_run", C.c_uint64),
+        ("rows_reset", C.c_uint64),
+        ("bytes_hdr", C.c_uint64),
+        ("bytes_run", C.c_uint64),
+        ("bytes_reset", C.c_uint64),
+        ("bytes_stored", C.c_uint64),
+        ("class_rows", C.c_uint64 * 5),
+        ("class_bytes", C.c_uint64 * 5),
+        ("apply_form", C.c_uint64),
+        ("host_pairs", C.c_uint64),
+        ("list_pairs", C.c_uint64),
+        ("audit_rows", C.c_uint64 * 5),
+    ]
+
+
 class TwMeasureSpec(C.Structure):
     """tw_measure_spec: the two TRACE tags to join and the histogram's shape."""
     _fields_ = [

@@ -17,8 +17,8 @@ from typing import Optional
 import numpy as np
 
 from .abi import (MEASURE_DTYPE, QUANTILE_DTYPE, RESULT_DTYPE, SERIES_DTYPE, SERIES_LATENCY, SERIES_MODES,
-                  SERIES_STAT_DTYPE, TwLiveDelays, TwLpState, TwMeasureOut, TwMeasureSpec, TwSeriesOut, TwSeriesSpec,
-                  TwStats, TwTableDraw)
+                  SERIES_STAT_DTYPE, TwLiveDelays, TwLpState, TwMeasureOut, TwMeasureSpec, TwPrefixRows, TwSeriesOut,
+                  TwSeriesSpec, TwStats, TwTableDraw)
 from .scenario import Scenario
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,7 +36,8 @@ EXPORTS = ["tw_create", "tw_comm_id", "tw_create_rank", "tw_ctx_info", "tw_lp_ru
            "tw_set_prefix", "tw_prefix_stats", "tw_set_measure_keys", "tw_measure_phases_ms",
            "tw_prefix_clean_stats", "tw_set_trace_batch", "tw_lp_set_trace", "tw_lp_read_trace", "tw_lp_measure",
            "tw_set_live_delays", "tw_live_stats", "tw_sweep_path_stats", "tw_measure_quantiles",
-           "tw_measure_quantiles_ms", "tw_measure_series", "tw_lp_measure_series", "tw_measure_series_ms"]
+           "tw_measure_quantiles_ms", "tw_measure_series", "tw_lp_measure_series", "tw_measure_series_ms",
+           "tw_prefix_rows_stats"]
 GEOMETRIES = ("dense", "sparse", "half", "wave", "lp", "narrow", "lpb", "compact")  # TW_GEO_* order
 
 # tw_trace_rec (include/timewarp.h)
@@ -142,6 +143,9 @@ def load_library(path: Optional[str] = None):
         lib.tw_prefix_clean_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         lib.tw_prefix_clean_stats.restype = C.c_int
+    if hasattr(lib, "tw_prefix_rows_stats"):  # (an older in-tree build under TW_LIB lacks it)
+        lib.tw_prefix_rows_stats.argtypes = [C.c_void_p, C.POINTER(TwPrefixRows)]
+        lib.tw_prefix_rows_stats.restype = C.c_int
     if hasattr(lib, "tw_sweep_path_stats"):  # (an older in-tree build under TW_LIB lacks it)
         lib.tw_sweep_path_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
         lib.tw_sweep_path_stats.restype = C.c_int
@@ -433,6 +437,29 @@ class Engine:
                                               C.byref(bad)), "tw_prefix_clean_stats")
         return {"claimed_slots": int(cl.value), "rows_skipped": int(rows.value), "bytes_stored": int(by.value),
                 "verified": bool(ver.value), "audit_mismatches": int(bad.value)}
+
+    ROW_CLASSES = ("none", "body", "hdr", "run", "reset")  # prefix_clean.hpp RC_*
+
+    def prefix_rows_stats(self) -> dict:
+        """The further rows the last run's apply left unstored, by class
+        (tw_prefix_rows_stats): header rows of claimed slots, run entries of
+        compared kill wakes, rows that hold what tw_reset leaves -- rows and
+        bytes per replica of each -- the bytes the apply really stored per
+        replica, and the cached snapshot's rows and bytes of every class; how
+        the apply ran (one workgroup per row and span, or over the list of the
+        pairs it stores, with the host's and the device's count of them) and,
+        under TW_TEST_PREFIX_AUDIT=1, the device's count of the rows it
+        skipped by class."""
+        o = TwPrefixRows()
+        _check(self.lib.tw_prefix_rows_stats(self.ctx, C.byref(o)), "tw_prefix_rows_stats")
+        return {"rows_hdr": int(o.rows_hdr), "rows_run": int(o.rows_run), "rows_reset": int(o.rows_reset),
+                "bytes_hdr": int(o.bytes_hdr), "bytes_run": int(o.bytes_run), "bytes_reset": int(o.bytes_reset),
+                "bytes_stored": int(o.bytes_stored),
+                "class_rows": dict(zip(self.ROW_CLASSES, (int(x) for x in o.class_rows))),
+                "class_bytes": dict(zip(self.ROW_CLASSES, (int(x) for x in o.class_bytes))),
+                "apply_form": ("none", "grid", "list")[int(o.apply_form)], "host_pairs": int(o.host_pairs),
+                "list_pairs": int(o.list_pairs),
+                "audit_rows": dict(zip(self.ROW_CLASSES, (int(x) for x in o.audit_rows)))}
 
     def set_live_delays(self, scn_or_arrays, seed_base: int = 0) -> "Engine":
         """Live delays (tw_set_live_delays): from now on a send over link l

@@ -10,9 +10,12 @@ arm "this library without the prefix" measured by bench.py's own loop.  `stats`
 leaves the prefix on and prints tw_prefix_stats after the last step to stderr
 (T0, the snapshot's events and bytes per replica, the apply's device time and
 its store rate over the batch; tw_prefix_clean_stats: the claimed slots, the
-rows the last apply skipped and the bytes it stored).  `noskip` leaves the
-prefix on but makes every apply store every row (a tw_set_prefix(1) before
-each run: any setter ends the last run's verification).  The result line is bench.py's in both cases.
+rows the last apply skipped and the bytes it stored; tw_prefix_rows_stats: the
+header, run-entry and reset-valued rows it skipped beside them and the bytes
+it really stored, which the stored rate is over).  `noskip` leaves the
+prefix on but makes every apply store every row the sweep would have to prove
+(a tw_set_prefix(1) before each run: any setter ends the last run's
+verification; the reset-valued rows stay skipped).  The result line is bench.py's in both cases.
 """
 import os
 import sys
@@ -43,9 +46,16 @@ def main():
                 st["apply_TBps"] = st["bytes"] * self.scn.n_replicas / (st["apply_ms"] * 1e-3) / 1e12
                 # (what the apply stored: tw_prefix_clean_stats' bytes, not the snapshot's)
                 cs = self.prefix_clean_stats()
-                st["stored_TBps"] = cs["bytes_stored"] * self.scn.n_replicas / (st["apply_ms"] * 1e-3) / 1e12
+                stored = cs["bytes_stored"]
+                rs = None
+                if hasattr(self.lib, "tw_prefix_rows_stats"):  # (an older build under TW_LIB lacks it)
+                    rs = self.prefix_rows_stats()
+                    stored = rs["bytes_stored"]  # (less the header, run-entry and reset-valued rows)
+                st["stored_TBps"] = stored * self.scn.n_replicas / (st["apply_ms"] * 1e-3) / 1e12
                 st.update(cs)
             print(f"[prefix] {st}", file=sys.stderr, flush=True)
+            if st["apply_ms"] > 0 and rs is not None:
+                print(f"[prefix rows] {rs}", file=sys.stderr, flush=True)
         close(self)
 
     run = Engine.run
