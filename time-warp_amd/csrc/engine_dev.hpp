@@ -1268,7 +1268,10 @@ struct Lane {
         th.r1 = b.x;                                     // link
         th.r2 = b.z;                                     // sending node
         th.r3 = b.y;                                     // kind
-        live += ok ? 1u : 0u;
+        // (the record was counted in `live` with the rest of its run, as the
+        // queued wake it stands for: with a slot the pop's own decrement takes
+        // it out, without one nothing pops and it leaves the count here)
+        live -= ok ? 0u : 1u;
         slot = ok ? s : 0u;
     }
 
@@ -2788,6 +2791,13 @@ tw_run_kernel(Dev c, int64_t t_end, uint64_t max_events, uint32_t budget) {
                 L.ds(DW_IB, (uint32_t)ib);
                 L.ds(DW_HN, dh | (dn << 16));
                 L.ds(DW_SQ0, (uint32_t)sc[SC_DUE_SEQ * SR]);
+                // the due run's records not yet popped count as live while the
+                // lane is in the kernel: each is a deliverer's wake queued at the
+                // window's start.  A lane whose own threads have all ended (a
+                // receiver after its `unlisten` and END) would otherwise stop at
+                // `live == 0` with its due run unpopped, every tick of a window
+                // that then never completes.  SC_LIVE itself stays without them.
+                L.live += dh < dn ? dn - dh : 0u;
                 uint4 h = make_uint4(0, 0, 0, 0);
                 if (dh < dn) h = gp(c.due)[(ib + (size_t)dh * ib_stride(c, !ilight)) * 2];
                 L.ds(DW_TL, h.x);
@@ -3098,7 +3108,12 @@ tw_run_kernel(Dev c, int64_t t_end, uint64_t max_events, uint32_t budget) {
             constexpr bool KEEP = !LP && RUNS;
             const uint64_t threads_add = (LP || KEEP) ? (uint64_t)L.d_th : (uint64_t)(L.tidc - (uint32_t)sc[SC_TIDC * SR]);
             sc[SC_NOW * SR] = (uint64_t)L.now; sc[SC_FINAL_T * SR] = (uint64_t)((LP || KEEP) ? L.final_t : L.now);
-            sc[SC_SEQ * SR] = L.seq; sc[SC_TIDC * SR] = L.tidc; sc[SC_LIVE * SR] = L.live;
+            uint32_t due_left = 0;  // (LP: the due run's unpopped records, counted in L.live)
+            if constexpr (LP) {
+                const uint32_t hn = L.dg(DW_HN);
+                due_left = (hn & 0xFFFFu) < (hn >> 16) ? (hn >> 16) - (hn & 0xFFFFu) : 0u;
+            }
+            sc[SC_SEQ * SR] = L.seq; sc[SC_TIDC * SR] = L.tidc; sc[SC_LIVE * SR] = L.live - due_left;
             sc[SC_NEAR_N * SR] = L.near_n; sc[SC_FAR_N * SR] = L.far_n;
             sc[SC_STATUS * SR] = L.status; sc[SC_MAIN_EXC * SR] = L.cg(CW_MAINEXC);
             sc[SC_FREE_N * SR] = L.free_n; sc[SC_FTOP * SR] = L.ftop; sc[SC_BUMP * SR] = L.bump;
