@@ -144,8 +144,9 @@ def test_lp_run_local_failure_agreed(engine_mod, oracle_mod, monkeypatch, mode):
     fails that shard's launches at that tick, as a HIP error would) does not
     strand the others in the exchange: every shard keeps exchanging and
     reducing until the batch's agreement, and tw_lp_run returns the agreed
-    code (TW_ERR_STATE) on all of them.  The next call sets the loop up again
-    and runs the scenario to the oracle's result."""
+    code (TW_ERR_STATE) on all of them.  The next call begins the loop again
+    (over the same exchange set-up: a failure at a tick does not undo it) and
+    runs the scenario to the oracle's result."""
     scn = scenarios.gossip(3000, drop_log2=4, seed=5)
     L = int(scn.meta["lookahead_us"])
     s = engine_mod.lp_scenario(scn)
@@ -164,6 +165,55 @@ def test_lp_run_local_failure_agreed(engine_mod, oracle_mod, monkeypatch, mode):
         assert int(agg[f]) == int(o.result[f]), (mode, f, int(agg[f]), o.result[f])
     assert np.array_equal(hashes, o.hashes)
     assert lp.done == 1 and lp.err == 0
+
+
+def test_lp_run_twice_after_local_failure(engine_mod, oracle_mod, monkeypatch):
+    """The copy transport's staging words and events are the context's, made
+    once: after a run that an agreed local failure ended part-way, two full
+    reset / run rounds on the same context, success after success on the same
+    objects, each equal the oracle."""
+    scn = scenarios.gossip(3000, drop_log2=4, seed=5)
+    s = engine_mod.lp_scenario(scn)
+    o = oracle_mod.run(scn, trace_cap=0)
+    with engine_mod.LPEngine(s, 0, scn.n_nodes, int(scn.meta["lookahead_us"]), devices=[0, 0]) as e:
+        e.reset()
+        monkeypatch.setenv("TW_TEST_FAIL_TICK", "1:5")
+        with pytest.raises(engine_mod.EngineError, match=r"tw_lp_run failed: -5 "):
+            e.run_lp()
+        monkeypatch.delenv("TW_TEST_FAIL_TICK")
+        for rnd in range(2):
+            e.reset()
+            lp = e.run_lp()
+            agg, hashes = e.lp_results()
+            for f in ("final_t", "events", "delivered", "dropped", "undeliverable", "status", "main_exc", "threads"):
+                assert int(agg[f]) == int(o.result[f]), (rnd, f, int(agg[f]), o.result[f])
+            assert np.array_equal(hashes, o.hashes), rnd
+            assert lp.done == 1 and lp.err == 0
+
+
+def test_lp_run_set_up_again_after_a_second_load(engine_mod, oracle_mod):
+    """A second tw_lp_load on one copy-transport context undoes the exchange
+    set-up, so the next tw_lp_run sets the loop up again, over the staging
+    words and events the first set-up left: the run before the second load and
+    two runs after it each equal the oracle."""
+    import ctypes
+
+    scn = scenarios.gossip(3000, drop_log2=4, seed=5)
+    L = int(scn.meta["lookahead_us"])
+    s = engine_mod.lp_scenario(scn)
+    o = oracle_mod.run(scn, trace_cap=0)
+    with engine_mod.LPEngine(s, 0, scn.n_nodes, L, devices=[0, 0]) as e:
+        for rnd in range(3):
+            if rnd == 1:
+                d = s.desc()
+                assert e.lib.tw_lp_load(e.ctx, ctypes.addressof(d), 0, scn.n_nodes, L, 16, 1 << 22) == 0
+            e.reset()
+            lp = e.run_lp()
+            agg, hashes = e.lp_results()
+            for f in ("final_t", "events", "delivered", "dropped", "undeliverable", "status", "main_exc", "threads"):
+                assert int(agg[f]) == int(o.result[f]), (rnd, f, int(agg[f]), o.result[f])
+            assert np.array_equal(hashes, o.hashes), rnd
+            assert lp.done == 1 and lp.err == 0
 
 
 @pytest.mark.parametrize("k", [1, 2, 3, 4])

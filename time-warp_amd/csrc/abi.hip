@@ -33,6 +33,7 @@
 
 #include "../../include/timewarp.h"
 #include "live_plan.hpp"
+#include "lp_run_plan.hpp"
 #include "lp_trace_plan.hpp"
 #include "measure_combine.hpp"
 #include "measure_select.hpp"
@@ -72,10 +73,11 @@ struct tw_ctx {
     uint32_t lp_begin = 0, lp_count = 0;
     bool lp_ready = false;                  // exchange buffers made for this load
     std::vector<uint32_t> starts;           // world + 1 node boundaries
-    std::vector<int64_t*> red_all;          // COPY: per shard [world][RD_N]
-    std::vector<hipEvent_t> ev_a, ev_b;     // COPY: per shard
+    // COPY, per shard: made once per context, reused by every set-up (lp_copy_objects)
+    std::vector<int64_t*> red_all;          // [world][RD_N]
+    std::vector<hipEvent_t> ev_a, ev_b;
     std::vector<void*> scratch;             // per shard: RCCL statistics buffer
-    uint32_t xcap = 1u << 14;               // exchange block stride (records per rank pair)
+    uint32_t xcap = LP_XCAP_DEFAULT;        // exchange block stride (records per rank pair)
     // an RCCL call of this context failed: the communicators may hold a
     // collective the peers are still in, so every later communicating call
     // returns TW_ERR_COMM without entering another one (timewarp.h, tw_lp_run)
@@ -155,8 +157,12 @@ bool nccl_test_fail(tw_ctx* c) { return c->test_fail_at > 0 && ++c->test_calls =
     } while (0)
 // ... between ncclGroupStart and ncclGroupEnd: a failure closes the group
 // first, so the thread is not left inside it (a later group of this thread --
-// a fresh context's -- would be folded into the open one); the broken
-// communicators are then aborted, not destroyed (destroy_parts)
+// a fresh context's -- would be folded into the open one).  That does not
+// contain the failure: closing the group launches what was already posted, so
+// peers that posted the full set stay blocked in the operations this rank
+// never posted until they abort on their own.  TW_ERR_COMM reaching the
+// caller must therefore abort the job.  This context's communicators are
+// aborted, not destroyed, but only at tw_destroy (destroy_parts)
 #define NCCLCHK_G(x)                                 \
     do {                                             \
         ncclResult_t _r = nccl_test_fail(c) ? ncclInternalError : (x); \
@@ -205,6 +211,15 @@ int each_shard(tw_ctx* c, F f) {
     for (auto& t : th) t.join();
     for (int r : rc)
         if (r != TW_OK) return r;
+    return TW_OK;
+}
+
+// enqueue on `st`, a stream of device dst_dev, a copy from device src_dev
+int copy_async(void* dst, int dst_dev, const void* src, int src_dev, size_t bytes, hipStream_t st) {
+    if (src_dev == dst_dev)
+        HIPCHK_A(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
+    else
+        HIPCHK_A(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, st));
     return TW_OK;
 }
 
@@ -257,32 +272,15 @@ int job_reduce(tw_ctx* c, std::vector<std::vector<uint64_t>>& sums, std::vector<
     return TW_OK;
 }
 
-// Status codes ranked by severity for the job-wide reduction (MAX): a hard
-// runtime, communicator or state failure on one shard outranks a replica
-// error or an incomplete run on another, whatever their numeric values
-int64_t sev_of(int rc) {
-    switch (rc) {
-    case TW_OK: return 0;
-    case TW_ERR_REPLICA: return 1;
-    case TW_ERR_INCOMPLETE: return 2;
-    case TW_ERR_INVALID: return 3;
-    case TW_ERR_STATE: return 4;
-    case TW_ERR_COMM: return 5;
-    case TW_ERR_OOM: return 6;
-    case TW_ERR_HIP: return 7;
-    default: return 8;  // TW_ERR_NO_DEVICE and anything unknown
-    }
-}
-int rc_of_sev(int64_t s) {
-    static const int rcs[] = {TW_OK, TW_ERR_REPLICA, TW_ERR_INCOMPLETE, TW_ERR_INVALID, TW_ERR_STATE,
-                              TW_ERR_COMM, TW_ERR_OOM, TW_ERR_HIP, TW_ERR_NO_DEVICE};
-    return s >= 0 && s <= 8 ? rcs[s] : TW_ERR_HIP;
-}
-
-// Every shard of every rank learns the worst of the shards' local codes (one
-// small all-reduce): a rank that failed locally joins the collective instead
-// of leaving the others waiting in the next one
+// Every shard of every rank learns the worst of the shards' local codes, by
+// their severity (sev_of, lp_run_plan.hpp), in one small all-reduce: a rank
+// that failed locally joins the collective instead of leaving the others
+// waiting in the next one
 int job_agree(tw_ctx* c, const std::vector<int>& local, int* worst) {
+    if (c->tp != TP_RCCL) {  // one process holds every shard
+        *worst = worst_of(local);
+        return TW_OK;
+    }
     const size_t n = c->sh.size();
     std::vector<std::vector<uint64_t>> sums(n, std::vector<uint64_t>{0});
     std::vector<std::vector<int64_t>> maxs(n);
@@ -348,12 +346,6 @@ void sub_desc(const tw_scenario_desc* s, uint32_t b0, uint32_t nb, SubDesc& o) {
     }
 }
 
-void split(uint32_t total, uint32_t parts, uint32_t i, uint32_t& b0, uint32_t& nb) {
-    const uint32_t base = total / parts, rem = total % parts;
-    b0 = i * base + std::min(i, rem);
-    nb = base + (i < rem ? 1u : 0u);
-}
-
 int destroy_parts(tw_ctx* c) {
     // (a failed call may have left a collective the peers never joined:
     // abort, which does not wait for it, instead of destroy)
@@ -373,6 +365,153 @@ int destroy_parts(tw_ctx* c) {
 }
 
 bool single(tw_ctx* c) { return c->sh.size() == 1; }
+
+// a device buffer released on every return
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { (void)hipFree(p); }
+};
+
+// ---- tw_lp_run's host side (its arithmetic: lp_run_plan.hpp).  Set-up, once
+// per load: node boundaries, the shards' exchange buffers, COPY's objects.
+
+// node boundaries of every rank -> c->starts
+int lp_boundaries(tw_ctx* c) {
+    const uint32_t world = (uint32_t)c->world;
+    if (!(c->tp == TP_RCCL && single(c) && world > 1)) {
+        lp_starts_even(c->lp_begin, c->lp_count, world, c->starts);
+        return TW_OK;
+    }
+    // one shard per process: all-gather (begin, count) over the ranks
+    DevBuf buf;
+    HIPCHK_A(hipSetDevice(c->dev[0]));
+    HIPCHK_A(hipMalloc(&buf.p, 8ull * (world + 1)));
+    const uint32_t mine[2] = {c->lp_begin, c->lp_count};
+    HIPCHK_A(hipMemcpy((char*)buf.p + 8ull * world, mine, 8, hipMemcpyHostToDevice));
+    NCCLCHK(ncclAllGather((char*)buf.p + 8ull * world, buf.p, 2, ncclUint32, c->comm[0], nullptr));
+    HIPCHK_A(hipStreamSynchronize(nullptr));
+    std::vector<uint32_t> h(2ull * world);
+    HIPCHK_A(hipMemcpy(h.data(), buf.p, 8ull * world, hipMemcpyDeviceToHost));
+    return lp_starts_gathered(h.data(), world, c->starts) ? TW_OK : TW_ERR_INVALID;
+}
+
+// COPY: every shard's staging words and two events.  They depend on world and
+// the shard count alone, so what a first set-up made every later one keeps
+// (and one that failed half-way is completed); destroy_parts frees them.
+int lp_copy_objects(tw_ctx* c) {
+    const size_t n = c->sh.size();
+    c->red_all.resize(n, nullptr);
+    c->ev_a.resize(n, nullptr);
+    c->ev_b.resize(n, nullptr);
+    for (size_t i = 0; i < n; ++i) {
+        HIPCHK_A(hipSetDevice(c->dev[i]));
+        if (!c->red_all[i]) HIPCHK_A(hipMalloc((void**)&c->red_all[i], 8ull * RD_N * c->world));
+        if (!c->ev_a[i]) HIPCHK_A(hipEventCreateWithFlags(&c->ev_a[i], hipEventDisableTiming));
+        if (!c->ev_b[i]) HIPCHK_A(hipEventCreateWithFlags(&c->ev_b[i], hipEventDisableTiming));
+    }
+    return TW_OK;
+}
+
+// A shard's local failure (lrc) from here on is carried to every rank by the
+// agreement before the next collective: no rank is left waiting in one.
+int lp_setup(tw_ctx* c, std::vector<int>& lrc) {
+    int rc = lp_boundaries(c);
+    if (rc) return rc;
+    c->xcap = lp_parse_xcap(getenv("TW_LP_XCAP"), c->xcap);
+    for (size_t i = 0; i < c->sh.size(); ++i)
+        lrc[i] = sh_lp_exchange_own(c->sh[i], (uint32_t)c->world, (uint32_t)(c->rank0 + i), c->starts.data(), c->xcap);
+    if (c->tp == TP_COPY) rc = lp_copy_objects(c);
+    c->lp_ready = !rc;
+    return rc;
+}
+
+// The transports of the loop.  What one call works on:
+struct LpLoop {
+    tw_ctx* c;
+    std::vector<ShardXchg> x;  // per shard: its stream, blocks and window words
+    size_t stride_b;           // bytes from one rank's block to the next
+};
+// ... and the two operations of a tick, chosen once per call
+struct LpTransport {
+    int (*blocks)(const LpLoop&, size_t bytes);  // block g of rank r's send -> block r of rank g's recv
+    int (*words)(const LpLoop&);                 // every rank's x.red <- the ranks' minimum, word by word
+};
+
+int rccl_blocks(const LpLoop& l, size_t bytes) {
+    tw_ctx* c = l.c;
+    NCCLCHK(ncclGroupStart());
+    for (size_t i = 0; i < l.x.size(); ++i)
+        for (int g = 0; g < c->world; ++g) {
+            const ShardXchg& x = l.x[i];
+            NCCLCHK_G(ncclSend((char*)x.send + g * l.stride_b, bytes, ncclUint8, g, c->comm[i], x.stream));
+            NCCLCHK_G(ncclRecv((char*)x.recv + g * l.stride_b, bytes, ncclUint8, g, c->comm[i], x.stream));
+        }
+    NCCLCHK_GEND();
+    return TW_OK;
+}
+
+int rccl_words(const LpLoop& l) {
+    tw_ctx* c = l.c;
+    NCCLCHK(ncclGroupStart());
+    for (size_t i = 0; i < l.x.size(); ++i)
+        NCCLCHK_G(ncclAllReduce(l.x[i].red, l.x[i].red, RD_N, ncclInt64, ncclMin, c->comm[i], l.x[i].stream));
+    NCCLCHK_GEND();
+    return TW_OK;
+}
+
+int nothing_from(size_t, size_t) { return TW_OK; }
+int nothing_then(size_t) { return TW_OK; }
+// COPY: one event round.  Every shard records ev on its stream; then every
+// shard i, its device current, makes its stream wait for each other shard g's
+// event right before from(i, g) enqueues what i takes from g (from(i, i)
+// waits for nothing), and runs then(i) behind all of them.
+template <class From, class Then = int (*)(size_t)>
+int copy_round(const LpLoop& l, const std::vector<hipEvent_t>& ev, From from, Then then = nothing_then) {
+    const tw_ctx* c = l.c;
+    const size_t n = l.x.size();
+    for (size_t i = 0; i < n; ++i) {
+        HIPCHK_A(hipSetDevice(c->dev[i]));
+        HIPCHK_A(hipEventRecord(ev[i], l.x[i].stream));
+    }
+    for (size_t i = 0; i < n; ++i) {
+        HIPCHK_A(hipSetDevice(c->dev[i]));
+        for (size_t g = 0; g < n; ++g) {
+            if (g != i) HIPCHK_A(hipStreamWaitEvent(l.x[i].stream, ev[g], 0));
+            const int rc = from(i, g);
+            if (rc) return rc;
+        }
+        const int rc = then(i);
+        if (rc) return rc;
+    }
+    return TW_OK;
+}
+
+int copy_blocks(const LpLoop& l, size_t bytes) {
+    const tw_ctx* c = l.c;
+    return copy_round(l, c->ev_a, [&](size_t i, size_t g) {
+        return copy_async((char*)l.x[i].recv + g * l.stride_b, c->dev[i], (const char*)l.x[g].send + i * l.stride_b,
+                          c->dev[g], bytes, l.x[i].stream);
+    });
+}
+
+int copy_words(const LpLoop& l) {
+    const tw_ctx* c = l.c;
+    const int rc = copy_round(l, c->ev_b, [&](size_t i, size_t g) {
+        return copy_async(c->red_all[i] + g * RD_N, c->dev[i], l.x[g].red, c->dev[g], 8 * RD_N, l.x[i].stream);
+    });
+    if (rc) return rc;
+    // every shard's copies of the others' words must land before any shard
+    // overwrites its own (its next tick's fill): a second event round orders
+    // the min after all copies
+    return copy_round(l, c->ev_a, nothing_from, [&](size_t i) -> int {
+        hipLaunchKernelGGL(tw_red_min, dim3(1), dim3(64), 0, l.x[i].stream, l.x[i].red, (const int64_t*)c->red_all[i],
+                           (uint32_t)l.x.size());
+        HIPCHK_A(hipGetLastError());
+        return TW_OK;
+    });
+}
+
+const LpTransport LP_RCCL{rccl_blocks, rccl_words}, LP_COPY{copy_blocks, copy_words};
 
 }  // namespace
 
@@ -1223,12 +1362,8 @@ int lp_trace_counts(tw_ctx* c, std::vector<uint64_t>& counts) {
 // them, > 0), gathered into one buffer on shard 0's device by copies ordered on
 // shard 0's stream, with the one replica's emitted count behind them.  The
 // caller synchronises that stream before the buffer goes.
-struct LpGather {
-    void* p = nullptr;
+struct LpGather : DevBuf {
     uint64_t* d_n = nullptr;
-    ~LpGather() {
-        if (p) (void)hipFree(p);
-    }
 };
 int lp_gather(tw_ctx* c, const LpTracePlan& p, LpGather* buf) {
     const int dev0 = c->dev[0];
@@ -1241,12 +1376,9 @@ int lp_gather(tw_ctx* c, const LpTracePlan& p, LpGather* buf) {
     }
     for (size_t i = 0; i < c->sh.size(); ++i) {
         if (!p.kept[i]) continue;
-        char* dst = (char*)buf->p + (size_t)p.off[i] * 32;
-        const size_t bytes = (size_t)p.kept[i] * 32;
-        if (c->dev[i] == dev0)
-            HIPCHK_A(hipMemcpyAsync(dst, sh_lp_trace_dev(c->sh[i]), bytes, hipMemcpyDeviceToDevice, st));
-        else
-            HIPCHK_A(hipMemcpyPeerAsync(dst, dev0, sh_lp_trace_dev(c->sh[i]), c->dev[i], bytes, st));
+        const int rc = copy_async((char*)buf->p + (size_t)p.off[i] * 32, dev0, sh_lp_trace_dev(c->sh[i]), c->dev[i],
+                                  (size_t)p.kept[i] * 32, st);
+        if (rc) return rc;
     }
     buf->d_n = (uint64_t*)((char*)buf->p + (size_t)p.emitted * 32);
     HIPCHK_A(hipMemcpyAsync(buf->d_n, &p.emitted, 8, hipMemcpyHostToDevice, st));
@@ -1385,26 +1517,15 @@ int tw_lp_measure_series(tw_ctx* c, const tw_series_spec* spec, tw_series_out* t
 // Blocks travel at the size the ranks last agreed on (the largest per-rank
 // demand of a tick, rounded up, re-chosen every 16 ticks from the reduced
 // words, so every rank picks the same); records beyond it wait a tick in the
-// carry buffer.  One host synchronisation per 16 ticks.
+// carry buffer.  One host synchronisation per 16 ticks.  A shard that failed
+// locally (lrc) stops launching but keeps taking part in the exchange and the
+// reduction until the batch's agreement.
 int tw_lp_run(tw_ctx* c, uint64_t max_ticks, tw_lp_state* out) {
     if (!c || !out) return TW_ERR_INVALID;
     if (c->comm_broken) return TW_ERR_COMM;
-    const size_t n = c->sh.size();
-    std::vector<int> lrc(n, TW_OK);  // each shard's first local failure
-    // the worst local code of the job (RCCL: agreed over every rank first)
-    auto agreed = [&](int* worst) -> int {
-        if (c->tp != TP_RCCL) {
-            int w = TW_OK;
-            for (int r : lrc)
-                if (sev_of(r) > sev_of(w)) w = r;
-            *worst = w;
-            return TW_OK;
-        }
-        return job_agree(c, lrc, worst);
-    };
     for (tw_shard* s : c->sh)
         if (!sh_is_lp(s)) return TW_ERR_STATE;
-    if (n == 1 && c->tp == TP_NONE) {
+    if (single(c) && c->tp == TP_NONE) {
         // one context, no transport: the shard's own loop
         const uint32_t st2[2] = {c->lp_begin, c->lp_begin + c->lp_count};
         int rc = sh_lp_exchange_setup(c->sh[0], 1, 0, st2, nullptr, nullptr, 0, nullptr);
@@ -1412,197 +1533,74 @@ int tw_lp_run(tw_ctx* c, uint64_t max_ticks, tw_lp_state* out) {
         if (!rc) rc = sh_lp_run_windows(c->sh[0], max_ticks, out);
         return rc;
     }
-    if (!c->lp_ready) {
-        // node boundaries of every rank
-        c->starts.assign((size_t)c->world + 1, 0);
-        if (c->tp == TP_RCCL && n == 1 && c->world > 1) {
-            // one shard per process: all-gather (begin, count) over the ranks
-            void* buf = nullptr;
-            HIPCHK_A(hipSetDevice(c->dev[0]));
-            HIPCHK_A(hipMalloc(&buf, 8ull * (c->world + 1)));
-            const uint32_t mine[2] = {c->lp_begin, c->lp_count};
-            HIPCHK_A(hipMemcpy((char*)buf + 8ull * c->world, mine, 8, hipMemcpyHostToDevice));
-            NCCLCHK(ncclAllGather((char*)buf + 8ull * c->world, buf, 2, ncclUint32, c->comm[0], nullptr));
-            HIPCHK_A(hipStreamSynchronize(nullptr));
-            std::vector<uint32_t> h(2ull * c->world);
-            HIPCHK_A(hipMemcpy(h.data(), buf, 8ull * c->world, hipMemcpyDeviceToHost));
-            HIPCHK_A(hipFree(buf));
-            for (int g = 0; g < c->world; ++g) {
-                c->starts[g] = h[2 * g];
-                if (g > 0 && h[2 * g] != h[2 * (g - 1)] + h[2 * (g - 1) + 1]) return TW_ERR_INVALID;  // not contiguous
-            }
-            c->starts[c->world] = h[2 * (c->world - 1)] + h[2 * (c->world - 1) + 1];
-        } else {
-            for (int g = 0; g < c->world; ++g) {
-                uint32_t b0, nb;
-                split(c->lp_count, (uint32_t)c->world, (uint32_t)g, b0, nb);
-                c->starts[g] = c->lp_begin + b0;
-            }
-            c->starts[c->world] = c->lp_begin + c->lp_count;
-        }
-        if (const char* x = getenv("TW_LP_XCAP")) {
-            const long v = strtol(x, nullptr, 10);
-            if (v >= 1 && v <= (1 << 22)) c->xcap = (uint32_t)v;
-        }
-        // (a shard's local failure from here on is carried to every rank by
-        // job_agree before the next collective: no rank is left waiting in one)
+    const size_t n = c->sh.size();
+    std::vector<int> lrc(n, TW_OK);  // each shard's first local failure
+    auto live = [&](auto f) {        // f on every shard that has not failed
         for (size_t i = 0; i < n; ++i)
-            if (!lrc[i]) lrc[i] = sh_lp_exchange_own(c->sh[i], (uint32_t)c->world, (uint32_t)(c->rank0 + i),
-                                                     c->starts.data(), c->xcap);
-        if (c->tp == TP_COPY) {
-            c->red_all.assign(n, nullptr);
-            c->ev_a.assign(n, nullptr);
-            c->ev_b.assign(n, nullptr);
-            for (size_t i = 0; i < n; ++i) {
-                HIPCHK_A(hipSetDevice(c->dev[i]));
-                HIPCHK_A(hipMalloc((void**)&c->red_all[i], 8ull * RD_N * c->world));
-                HIPCHK_A(hipEventCreateWithFlags(&c->ev_a[i], hipEventDisableTiming));
-                HIPCHK_A(hipEventCreateWithFlags(&c->ev_b[i], hipEventDisableTiming));
-            }
-        }
-        c->lp_ready = true;
-    }
-    std::vector<ShardXchg> x(n);
+            if (!lrc[i]) lrc[i] = f(c->sh[i]);
+    };
+    int worst = TW_OK;
+    int rc = c->lp_ready ? TW_OK : lp_setup(c, lrc);
+    if (rc) return rc;
+    LpLoop l{c, std::vector<ShardXchg>(n), 0};
     uint32_t cap_eff = 0;
     for (size_t i = 0; i < n; ++i) {
         if (!lrc[i]) lrc[i] = sh_lp_loop_begin(c->sh[i]);
-        if (!lrc[i]) sh_lp_exchange_info(c->sh[i], &x[i]);
-        if (!lrc[i]) cap_eff = std::min<uint32_t>(x[i].stride, 4096u);
+        if (lrc[i]) continue;
+        sh_lp_exchange_info(c->sh[i], &l.x[i]);
+        cap_eff = lp_first_block(l.x[i].stride);
     }
-    for (size_t i = 0; i < n; ++i)
-        if (!lrc[i]) lrc[i] = sh_lp_set_block(c->sh[i], cap_eff);
-    {
-        int worst = TW_OK;
-        const int rc = agreed(&worst);
-        if (rc) return rc;
-        if (worst) {
-            if (c->lp_ready) c->lp_ready = false;  // (set up again by the next call)
-            return worst;
-        }
+    live([&](tw_shard* s) { return sh_lp_set_block(s, cap_eff); });
+    rc = job_agree(c, lrc, &worst);
+    if (rc) return rc;
+    if (worst) {
+        c->lp_ready = false;  // (set up again by the next call)
+        return worst;
     }
-    const size_t stride_b = 32ull * ((size_t)x[0].stride + 1);
-    std::vector<tw_lp_state> st(n);
+    const uint32_t stride = l.x[0].stride;
+    l.stride_b = lp_block_bytes(stride);
+    const LpTransport& tp = c->tp == TP_RCCL ? LP_RCCL : LP_COPY;
     // testing hook: TW_TEST_FAIL_TICK=shard:tick makes that local shard's
     // launches at that tick fail (TW_ERR_STATE), as a HIP or launch error
     // would -- the other shards and ranks must still leave together
-    long fail_sh = -1, fail_tk = -1;
-    if (const char* f = getenv("TW_TEST_FAIL_TICK")) {
-        char* e = nullptr;
-        fail_sh = strtol(f, &e, 10);
-        fail_tk = (e && *e == ':') ? strtol(e + 1, nullptr, 10) : -1;
-    }
+    const LpFailAt fail = lp_parse_fail_tick(getenv("TW_TEST_FAIL_TICK"));
+    std::vector<tw_lp_state> st(n);
     for (uint64_t done_ticks = 0; done_ticks < max_ticks;) {
         const uint64_t batch = std::min<uint64_t>(max_ticks - done_ticks, 16);
-        const size_t bytes = 32ull * ((size_t)cap_eff + 1);
+        const size_t bytes = lp_block_bytes(cap_eff);
         for (uint64_t k = 0; k < batch; ++k) {
-            // a shard that failed stops launching but keeps taking part in the
-            // exchange and the reduction until the batch's agreement
-            for (size_t i = 0; i < n; ++i) {
-                if (!lrc[i]) lrc[i] = sh_lp_tick(c->sh[i]);
-                if (!lrc[i] && (long)i == fail_sh && (long)(done_ticks + k) == fail_tk) lrc[i] = TW_ERR_STATE;
-            }
-            // record blocks: block g of rank r's send -> block r of rank g's recv
-            if (c->tp == TP_RCCL) {
-                NCCLCHK(ncclGroupStart());
-                for (size_t i = 0; i < n; ++i)
-                    for (int g = 0; g < c->world; ++g) {
-                        NCCLCHK_G(ncclSend((char*)x[i].send + g * stride_b, bytes, ncclUint8, g, c->comm[i], x[i].stream));
-                        NCCLCHK_G(ncclRecv((char*)x[i].recv + g * stride_b, bytes, ncclUint8, g, c->comm[i], x[i].stream));
-                    }
-                NCCLCHK_GEND();
-            } else {
-                for (size_t i = 0; i < n; ++i) {
-                    HIPCHK_A(hipSetDevice(c->dev[i]));
-                    HIPCHK_A(hipEventRecord(c->ev_a[i], x[i].stream));
-                }
-                for (size_t i = 0; i < n; ++i) {
-                    HIPCHK_A(hipSetDevice(c->dev[i]));
-                    for (size_t g = 0; g < n; ++g) {
-                        if (g != i) HIPCHK_A(hipStreamWaitEvent(x[i].stream, c->ev_a[g], 0));
-                        char* dst = (char*)x[i].recv + g * stride_b;
-                        const char* src = (const char*)x[g].send + i * stride_b;
-                        if (c->dev[g] == c->dev[i])
-                            HIPCHK_A(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, x[i].stream));
-                        else
-                            HIPCHK_A(hipMemcpyPeerAsync(dst, c->dev[i], src, c->dev[g], bytes, x[i].stream));
-                    }
-                }
-            }
+            live(sh_lp_tick);
             for (size_t i = 0; i < n; ++i)
-                if (!lrc[i]) lrc[i] = sh_lp_tick_import(c->sh[i]);
-            // window words: all-reduce(min)
-            if (c->tp == TP_RCCL) {
-                NCCLCHK(ncclGroupStart());
-                for (size_t i = 0; i < n; ++i)
-                    NCCLCHK_G(ncclAllReduce(x[i].red, x[i].red, RD_N, ncclInt64, ncclMin, c->comm[i], x[i].stream));
-                NCCLCHK_GEND();
-            } else {
-                for (size_t i = 0; i < n; ++i) {
-                    HIPCHK_A(hipSetDevice(c->dev[i]));
-                    HIPCHK_A(hipEventRecord(c->ev_b[i], x[i].stream));
-                }
-                for (size_t i = 0; i < n; ++i) {
-                    HIPCHK_A(hipSetDevice(c->dev[i]));
-                    for (size_t g = 0; g < n; ++g) {
-                        if (g != i) HIPCHK_A(hipStreamWaitEvent(x[i].stream, c->ev_b[g], 0));
-                        if (c->dev[g] == c->dev[i])
-                            HIPCHK_A(hipMemcpyAsync(c->red_all[i] + g * RD_N, x[g].red, 8 * RD_N,
-                                                    hipMemcpyDeviceToDevice, x[i].stream));
-                        else
-                            HIPCHK_A(hipMemcpyPeerAsync(c->red_all[i] + g * RD_N, c->dev[i], x[g].red, c->dev[g],
-                                                        8 * RD_N, x[i].stream));
-                    }
-                }
-                // every shard's copies of the others' words must land before any
-                // shard overwrites its own (its next tick's fill): a second event
-                // round orders the min after all copies
-                for (size_t i = 0; i < n; ++i) {
-                    HIPCHK_A(hipSetDevice(c->dev[i]));
-                    HIPCHK_A(hipEventRecord(c->ev_a[i], x[i].stream));
-                }
-                for (size_t i = 0; i < n; ++i) {
-                    HIPCHK_A(hipSetDevice(c->dev[i]));
-                    for (size_t g = 0; g < n; ++g)
-                        if (g != i) HIPCHK_A(hipStreamWaitEvent(x[i].stream, c->ev_a[g], 0));
-                    hipLaunchKernelGGL(tw_red_min, dim3(1), dim3(64), 0, x[i].stream, x[i].red,
-                                       (const int64_t*)c->red_all[i], (uint32_t)n);
-                    HIPCHK_A(hipGetLastError());
-                }
-            }
-            for (size_t i = 0; i < n; ++i)
-                if (!lrc[i]) lrc[i] = sh_lp_tick_end(c->sh[i]);
+                if (!lrc[i] && fail.hit(i, done_ticks + k)) lrc[i] = TW_ERR_STATE;
+            rc = tp.blocks(l, bytes);
+            if (rc) return rc;
+            live(sh_lp_tick_import);
+            rc = tp.words(l);
+            if (rc) return rc;
+            live(sh_lp_tick_end);
         }
         done_ticks += batch;
-        bool err = false, done = true;
+        bool done = true;
         for (size_t i = 0; i < n; ++i) {
             if (!lrc[i]) lrc[i] = sh_lp_progress(c->sh[i], &st[i]);
-            err = err || st[i].err;
             done = done && st[i].done;
         }
-        {
-            int worst = TW_OK;
-            const int rc = agreed(&worst);
-            if (rc) return rc;
-            if (worst) return worst;
-        }
+        rc = job_agree(c, lrc, &worst);
+        if (rc) return rc;
+        if (worst) return worst;
         *out = st[0];
         for (size_t i = 1; i < n; ++i) out->err |= st[i].err;
-        if (err) return TW_ERR_REPLICA;
+        if (out->err) return TW_ERR_REPLICA;
         if (done) return TW_OK;
-        // the next batch's block size, from the largest demand any rank had in
-        // one tick (reduced, so identical on every rank)
-        const int64_t dem = sh_lp_xmax(c->sh[0]);
-        uint32_t want = 64;
-        while (want < (uint64_t)dem + (uint64_t)dem / 4 && want < x[0].stride) want <<= 1;
-        want = std::min(want, x[0].stride);
-        if (want > cap_eff || want * 4 <= cap_eff) cap_eff = want;
-        for (size_t i = 0; i < n; ++i) {
-            if (!lrc[i]) lrc[i] = sh_lp_set_block(c->sh[i], cap_eff);
-            if (!lrc[i]) lrc[i] = sh_lp_clear_xmax(c->sh[i]);
-        }
+        // the largest demand any rank had in one tick is reduced, so every
+        // rank picks the same next block
+        cap_eff = lp_next_block(sh_lp_xmax(c->sh[0]), stride, cap_eff);
+        live([&](tw_shard* s) {
+            const int e = sh_lp_set_block(s, cap_eff);
+            return e ? e : sh_lp_clear_xmax(s);
+        });
     }
-    int worst = TW_OK;
-    const int rc = agreed(&worst);
+    rc = job_agree(c, lrc, &worst);
     if (rc) return rc;
     return worst ? worst : TW_ERR_INCOMPLETE;
 }
